@@ -1,11 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X EC + checksum hot path (driver contract: one JSON line on rank 0).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|...]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|...] [--dump-outputs DIR] [--full]
 
 Default workload = BASELINE.json configs[1]: rs-6-3-1024k encode of 4096 stripes per GPU, device-resident.
 A "step" is one ozec_encode_batch over the GPU's 4096 stripes (24 GiB of data cells read, 12 GiB of parity
 written).
+
+A plain run sets up the workload, runs W untimed and K timed steps and prints the line: value, ms_per_step and the
+roofline fraction from the HIP events around the timed steps.  --dump-outputs DIR then also writes what the last timed
+step computed (the workload's parity / rebuilt units / CRCs / mismatch indexes) as DIR/<name>.npy; the inputs are
+seeded, so two builds run with the same arguments can be compared file by file.  Everything below the value line
+(traffic, legs, e2e, JNI rows, cpu_baseline) takes runs of its own and is measured only with --full.
 
 Multi-GPU: one process per GPU.  Under torchrun the ranks come from the environment; with
 `--gpus N` and no WORLD_SIZE this script starts the N rank processes itself (before anything touches a GPU) and
@@ -15,12 +21,12 @@ torch.distributed only carries barriers and max-over-ranks reductions of the tim
 
 value        = data bytes of all ranks / max-over-ranks wall time of the K timed steps (GB = 1e9 B)
 roofline     = algorithmic bytes per launch / mean kernel time from HIP events on the launch stream (max over
-               ranks), against 8.0 TB/s; `traffic` = HBM bytes per launch of the same kernel measured by this run
-               in two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE, gfx950 correction), N = 1 only
-e2e          = BASELINE configs[4] (C5) at the same N: one batch of 8192 rs-6-3-1024k stripes in shared host
+               ranks), against 8.0 TB/s; `traffic` (--full) = HBM bytes per launch of the same kernel measured by
+               this run in two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE, gfx950 correction), N = 1 only
+e2e          = (--full) BASELINE configs[4] (C5) at the same N: one batch of 8192 rs-6-3-1024k stripes in shared host
                memory, each GPU encoding + CRC32C'ing its stripe range from NUMA-local pinned pages
                (ozec_encode_crc_host_batch), parity and CRCs back into the batch
-cpu_baseline = (rank 0, N = 1) oracle/cpu_baseline.c compiled -march=native on this host and run on a bounded
+cpu_baseline = (--full; rank 0, N = 1) oracle/cpu_baseline.c compiled -march=native on this host and run on a bounded
                sample of the same work with T = the CPUs this process may use and with 1 thread
 """
 import argparse
@@ -90,7 +96,20 @@ def parse(argv=None):
     ap.add_argument("--queue-batch", type=int, default=32, help="queue workloads: stripes per GPU batch")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="ozec_set_tuning knob (A/B and profiling runs only; defaults are the measured best)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the line can carry: the device-resident legs, "
+                         "the C5 end-to-end legs, the rocprofv3 PMC passes, the JNI per-call rows and the CPU baselines "
+                         "(each still has its --no-* switch); without it a run sets up, warms up, times the steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (float32 / float64; "
+                         "a fixed seeded sample of outputs larger than the 32 MiB the files may take together)")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.workload in ("c5", "legs", "jni", "tail", "stream"):
+        ap.error(f"--dump-outputs: the {args.workload} workload is a set of rows, not one timed path with outputs")
+    if not args.full:  # a plain run measures its headline figure only
+        args.no_cpu = args.no_e2e = args.no_pmc = args.no_legs = args.no_inproc = args.no_jni = True
+    return args
 
 
 # ------------------------------------------------------------------------------------------ launch
@@ -234,6 +253,7 @@ class Workload:
                 for th in ts:
                     th.join()
             self._step = step
+            self._outputs = lambda: {"parity": np.stack([np.stack(c) for c in self.hp])}
             return
         if name == "c3r_host":
             # reconstruction end to end from pinned host memory: the reconstruction coordinator's read buffers
@@ -279,6 +299,7 @@ class Workload:
                                                self.crc_type, self.bpc, hocrc32, h_expected=hexp32, h_mismatch=hmis32)
             self._step = step
             self._check = lambda: bool((hmis32 == -1).all())
+            self._outputs = lambda: {"rebuilt": hout, "rebuilt_crc": hocrc32, "mismatch": hmis32}
             return
         if name in ("queue", "queue_pageable"):
             from ozone_amd.stripe_queue import StripeQueue, host_alloc
@@ -322,6 +343,7 @@ class Workload:
                     t = self.q.submit(self.qd[j], self.qp[j], crcs=self.qc[j])
                 self.q.wait(t)
             self._step = step
+            self._outputs = lambda: {"parity": np.stack([np.stack(c) for c in self.qp]), "crc": np.stack(self.qc)}
             return
         if name == "c1":
             k, p, S = 3, 2, stripes_override or 1024
@@ -350,6 +372,7 @@ class Workload:
                 self.config = {"workload": "CRC32C per 16 KiB window, device-resident", "cells": S, "cell_bytes": n,
                                "bytes_per_checksum": self.bpc}
                 self._step = lambda: ck.checksum_windows_batch(self.crc_type, self.data, n, S, n, self.bpc, self.crcs)
+                self._outputs = lambda: {"crc": self.crcs}
             else:
                 ck.checksum_windows_batch(self.crc_type, self.data, n, S, n, self.bpc, self.crcs)
                 self.mism = torch.empty(S, dtype=torch.int32, device=dev)
@@ -361,6 +384,7 @@ class Workload:
                                "bytes_per_checksum": self.bpc}
                 self._step = lambda: ck.checksum_verify_batch(self.crc_type, self.data, n, S, n, self.bpc, self.crcs,
                                                               self.mism)
+                self._outputs = lambda: {"mismatch": self.mism}
             torch.cuda.synchronize()
             return
         units = k + p
@@ -385,6 +409,7 @@ class Workload:
 
             self._step = lambda: enc.encode_crc_block_groups(self.blocks, units * us, us, G, B, n, self.crc_type,
                                                              self.bpc, self.crcs)
+            self._outputs = lambda: {"parity": self.blocks[:, k:], "crc": self.crcs}
             torch.cuda.synchronize()
             return
         # HBM layout: stripe-major, units contiguous: unit u of stripe s at s*(k+p)*n + u*n
@@ -392,6 +417,7 @@ class Workload:
         for u in range(k):
             rc.fill_splitmix64_cells(self.units[:, u], units * n, S, n, SEED, u * S * world + self.lo)
         stride = units * n
+        self._outputs = lambda: {"parity": self.units[:, k:]}  # c1 / c2; the other workloads set their own
         if name == "c1":
             self.data_bytes = S * k * n
             self.alg_bytes = S * units * n
@@ -422,6 +448,7 @@ class Workload:
                            "codec": "rs", "data_units": k, "parity_units": p, "cell_bytes": n, "stripes": S}
             self._step = lambda: self.dec.decode_batch(self.units, stride, n, present, self.erased, self.out, 4 * n,
                                                        n, S, n)
+            self._outputs = lambda: {"rebuilt": self.out}
         elif name == "c3r":
             enc.encode_batch(self.units, stride, n, self.units[:, k:], stride, n, S, n)
             self.dec = rc.RawErasureDecoder(rc.ECReplicationConfig(k, p))
@@ -444,6 +471,7 @@ class Workload:
                 self.units, stride, n, present, self.erased, self.out, 4 * n, n, S, n, self.crc_type, self.bpc,
                 self.out_crc, d_expected=self.stored, d_mismatch=self.mism)
             self._check = lambda: bool((self.mism == -1).all().item())  # every stripe's read units verified
+            self._outputs = lambda: {"rebuilt": self.out, "rebuilt_crc": self.out_crc, "mismatch": self.mism}
         else:  # c4s (xor-2-1 stripe-major) / c5dev (rs-6-3): fused encode + CRC, device-resident
             self.crcs = torch.empty((S, units, self.nwin), dtype=torch.int32, device=dev)
             self.data_bytes = S * k * n
@@ -456,10 +484,15 @@ class Workload:
                            "bytes_per_checksum": self.bpc}
             self._step = lambda: enc.encode_crc_batch(self.units, stride, n, self.units[:, k:], stride, n, S, n,
                                                       self.crc_type, self.bpc, self.crcs)
+            self._outputs = lambda: {"parity": self.units[:, k:], "crc": self.crcs}
         torch.cuda.synchronize()
 
     def step(self):
         self._step()
+
+    def outputs(self):
+        """{name: array} of what one step hands its caller: device tensors or host arrays, views where possible"""
+        return self._outputs()
 
     def free(self):
         for a in ("units", "blocks", "data", "crcs", "stored", "out", "out_crc", "mism"):
@@ -997,6 +1030,44 @@ def time_workload(wl, steps, warmup, dist):
     barrier()
     elapsed = time.perf_counter() - t0
     return elapsed, float(np.mean([a.elapsed_time(b) for a, b in ev]))
+
+
+DUMP_BYTES = 32 << 20  # --dump-outputs: the .npy payloads of one rank together
+DUMP_RUN = 256  # a sampled output is taken in runs of this many consecutive elements
+
+
+def _dump_array(a, cap):
+    """`a` (a device tensor or a host array of any strides) as a float array that holds its values exactly: uint8 ->
+    float32, 32-bit CRCs (as stored: int32 or uint32) and mismatch indexes -> float64.  More than `cap` elements are sampled: the row-major
+    flattening is cut into cap / DUMP_RUN equal spans and one run of DUMP_RUN elements is taken from each, at an offset
+    drawn from a generator seeded with SEED, so the same arguments pick the same elements in every run and build."""
+    shape = tuple(a.shape)
+    n = int(np.prod(shape, dtype=np.int64))
+    idx = None
+    if n > cap:
+        runs = max(1, cap // DUMP_RUN)
+        span = n // runs
+        offset = np.random.default_rng(SEED).integers(0, span - DUMP_RUN + 1, runs)
+        start = np.arange(runs, dtype=np.int64) * span + offset
+        idx = np.unravel_index((start[:, None] + np.arange(DUMP_RUN, dtype=np.int64)).reshape(-1), shape)
+    if torch.is_tensor(a):
+        if idx is not None:
+            a = a[tuple(to_dev(i, a.device) for i in idx)]
+        h = to_host(a)
+    else:
+        h = np.asarray(a)[idx] if idx is not None else np.array(a)
+    return h.astype(np.float32 if h.dtype == np.uint8 else np.float64)
+
+
+def dump_outputs(outputs, out_dir, rank, world):
+    """--dump-outputs: one DIR/<name>.npy per output of the timed path's last step (DIR/<name>.rank<r>.npy for the
+    ranks of a multi-GPU run), DUMP_BYTES in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(outputs))
+    for name, a in outputs.items():
+        itemsize = 4 if a.dtype in (torch.uint8, np.uint8) else 8
+        arr = _dump_array(a, share // itemsize)
+        np.save(os.path.join(out_dir, f"{name}.npy" if world == 1 else f"{name}.rank{rank}.npy"), arr)
 
 
 def device_legs(args, rank, world, dist, red_dev):
@@ -1556,6 +1627,9 @@ def main():
         result["roofline"]["note"] = "kernel_ms is the whole PCIe-inclusive step; the bound is the link, not HBM"
     if hasattr(wl, "_check"):
         result["verified"] = wl._check()
+    if args.dump_outputs:
+        log(f"writing the last step's outputs to {args.dump_outputs}")
+        dump_outputs(wl.outputs(), args.dump_outputs, rank, world)
     wl.free()
     del wl
     if args.workload == "c2" and not args.no_legs:
@@ -1597,7 +1671,7 @@ def main():
             if "e2e" in result and "value" in result["e2e"]:
                 result["e2e"]["cpu_baseline"] = cpu_baseline("c5", args.cpu_seconds)
     if rank == 0:
-        if args.workload == "c2" and not args.full_line:
+        if args.workload == "c2" and args.full and not args.full_line:
             emit_default(result)
         else:
             emit(result)

@@ -4,6 +4,7 @@
 // "current" policy, per-thread devices of coder-less calls (re-picked after the list changes), and DeviceScope
 // restoring the caller's device.
 #include <hip/hip_runtime.h>
+#include <sched.h>
 #include <sys/syscall.h>
 #include <unistd.h>
 
@@ -63,6 +64,14 @@ int main(int argc, char **argv) {
   }
   unsigned cpu = 0, node = 0;
   syscall(SYS_getcpu, &cpu, &node, nullptr);
+  // the NUMA checks below call "the caller's node" one node: keep this thread and the threads it starts on the CPU it
+  // runs on now (on a host with several nodes the scheduler may otherwise start a thread on another one)
+  cpu_set_t here;
+  CPU_ZERO(&here);
+  if (cpu < CPU_SETSIZE) {
+    CPU_SET(cpu, &here);
+    if (sched_setaffinity(0, sizeof here, &here) == 0) syscall(SYS_getcpu, &cpu, &node, nullptr);
+  }
   // devices 0, 1 on another node than the caller's; 2, 3 on the caller's
   g_node_of[0] = g_node_of[1] = static_cast<int>(node) + 1;
   g_node_of[2] = g_node_of[3] = static_cast<int>(node);

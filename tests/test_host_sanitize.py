@@ -9,6 +9,8 @@ import subprocess
 
 import pytest
 
+import noaslr
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "ozone_amd", "csrc")
 ROCM = "/opt/rocm"
@@ -35,7 +37,8 @@ def _build(tmp_path, name, sanitize):
 
 def _run(exe, mode, env_key, env_val):
     env = dict(os.environ, **{env_key: env_val})
-    r = subprocess.run([str(exe), mode], capture_output=True, text=True, timeout=300, env=env)
+    r = subprocess.run([str(exe), mode], capture_output=True, text=True, timeout=300, env=env,
+                       preexec_fn=noaslr.no_aslr if env_key == "TSAN_OPTIONS" else None)
     assert r.returncode == 0, r.stdout + r.stderr[-4000:]
     assert "ok" in r.stdout, r.stdout
     return r.stdout

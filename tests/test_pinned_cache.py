@@ -9,6 +9,8 @@ import tempfile
 
 import pytest
 
+import noaslr
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -27,6 +29,6 @@ def binary():
 
 
 def test_pinned_block_cache(binary):
-    r = subprocess.run([binary], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([binary], capture_output=True, text=True, timeout=120, preexec_fn=noaslr.no_aslr)
     assert r.returncode == 0, r.stderr[-3000:]
     assert "pinned blocks OK" in r.stdout

@@ -7,6 +7,8 @@ import tempfile
 
 import pytest
 
+import noaslr
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -25,6 +27,6 @@ def binary():
 
 
 def test_work_slot_pool(binary):
-    r = subprocess.run([binary], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([binary], capture_output=True, text=True, timeout=120, preexec_fn=noaslr.no_aslr)
     assert r.returncode == 0, r.stderr[-3000:]
     assert "work slots OK" in r.stdout
