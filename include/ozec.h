@@ -46,6 +46,8 @@ extern "C" {
 #define OZEC_CHECKSUM_NONE 1
 #define OZEC_CHECKSUM_CRC32 2
 #define OZEC_CHECKSUM_CRC32C 3
+#define OZEC_CHECKSUM_SHA256 4    /* window digests: ozec_digest_* below; every other entry point takes the CRC types only */
+#define OZEC_CHECKSUM_MD5 5
 
 #define OZEC_MAX_K 64             /* data units handled by the GPU kernels      */
 #define OZEC_MAX_ROWS 16          /* parity rows / erased units per call        */
@@ -221,6 +223,30 @@ int ozec_checksum_verify_batch(int checksum_type, const uint8_t *d_base, int64_t
                                size_t len, size_t bytes_per_checksum, const uint32_t *d_expected,
                                int expected_big_endian, int32_t *d_mismatch, void *stream);
 
+/* ---- SHA256 / MD5 window digests: Checksum.computeChecksum for ChecksumType SHA256 / MD5, i.e.
+ *      MessageDigest.getInstance("SHA-256" / "MD5") per bytesPerChecksum window (CM/Checksum.java:43-57,76-81) over
+ *      ChunkBufferImplWithByteBuffer.iterate (CM/ChunkBufferImplWithByteBuffer.java:78-98).  One digest per window,
+ *      ceil(len / bpc) of them, the last window short; each is the bytes MessageDigest.digest() returns (32 for SHA256,
+ *      16 for MD5), stored densely: out[c][w][digest_len].  No endian flag.  On the GPU one lane hashes one window, so
+ *      a call needs many windows to fill the device and a single very large window is one lane's serial work.
+ *      checksum_type must be OZEC_CHECKSUM_SHA256 or OZEC_CHECKSUM_MD5 (CRC types: ozec_checksum_windows*);
+ *      len == 0 or num_cells == 0 writes nothing; argument errors are reported before any device is touched. ---- */
+size_t ozec_digest_length(int checksum_type); /* MessageDigest.getDigestLength(): 32, 16; 0 for every other type */
+/* host buffer (Checksum.computeChecksum(ByteBuffer), CM/Checksum.java:132-200): staged through the calling thread's
+ * GPU in chunks of whole windows; registered / pinned / pageable buffers are treated as by ozec_checksum_windows */
+int ozec_digest_windows(int checksum_type, const uint8_t *data, size_t len, size_t bytes_per_checksum, uint8_t *out);
+int ozec_digest_windows_device(int checksum_type, const uint8_t *d_data, size_t len, size_t bytes_per_checksum,
+                               uint8_t *d_out, void *stream);
+/* many equally sized cells: cell c at d_base + c*cell_stride (any byte address, cell_stride >= len) */
+int ozec_digest_windows_batch(int checksum_type, const uint8_t *d_base, int64_t cell_stride, size_t num_cells,
+                              size_t len, size_t bytes_per_checksum, uint8_t *d_out, void *stream);
+/* Checksum.verifyChecksum + ChecksumData.verifyChecksumDataMatches (CM/Checksum.java:241-297,
+ * CM/ChecksumData.java:118-150) over many chunks, as ozec_checksum_verify_batch: d_expected[c][w][digest_len] are the
+ * stored ByteString bytes; d_mismatch[c] = -1 when every window matches, else the first failing window index. */
+int ozec_digest_verify_batch(int checksum_type, const uint8_t *d_base, int64_t cell_stride, size_t num_cells,
+                             size_t len, size_t bytes_per_checksum, const uint8_t *d_expected, int32_t *d_mismatch,
+                             void *stream);
+
 /* ---- fused reconstruction, one pass over HBM for what
  *      ECReconstructionCoordinator.reconstructECBlockGroup (ECReconstructionCoordinator.java:240-352) does in three:
  *      verify the stored CRCs of the units read (ChunkInputStream.java:493-506), decode the erased units
@@ -377,8 +403,8 @@ int ozec_crc_compose_windows_batch(int checksum_type, const uint32_t *d_crcs, in
 #define OZEC_OP_DECODE_DEVICE 3   /* ozec_decode_device / ozec_decode_batch                                 */
 #define OZEC_OP_FUSED 4           /* ozec_encode_crc_batch / _block_groups / ozec_reconstruct_crc_batch      */
 #define OZEC_OP_HOST_BATCH 5      /* ozec_encode_crc_host_batch / ozec_reconstruct_crc_host_batch           */
-#define OZEC_OP_CHECKSUM 6        /* ozec_checksum_windows / _verify / ozec_crc_update (host buffers)       */
-#define OZEC_OP_CHECKSUM_DEVICE 7 /* ozec_checksum_windows_batch / _device / ozec_checksum_verify_batch     */
+#define OZEC_OP_CHECKSUM 6        /* ozec_checksum_windows / _verify / ozec_crc_update / ozec_digest_windows (host buffers) */
+#define OZEC_OP_CHECKSUM_DEVICE 7 /* ozec_checksum_windows_batch / _device / ozec_checksum_verify_batch, ozec_digest_*_batch / _device */
 #define OZEC_OP_QUEUE 8           /* ozec_stripe_queue_submit / _flush / _wait                              */
 #define OZEC_NUM_OPS 9
 typedef struct {

@@ -9,8 +9,9 @@ import org.apache.ozone.erasurecode.rawcoder.OzecNative;
  * ServiceLoader) finds in this jar through META-INF/services/org.apache.hadoop.ozone.common.ChecksumAccelerator.
  *
  * <p>hdds-common never names this class or anything else in this jar: without the jar on the class path, or with
- * libozec_jni unusable, or with neither opt-in threshold set ({@code ozone.checksum.hip.min.bytes} for the streaming
- * CRC, {@code ozone.checksum.hip.batch.min.bytes} for the batch), {@link #isAvailable} is false or the provider is never
+ * libozec_jni unusable, or with no opt-in threshold set ({@code ozone.checksum.hip.min.bytes} for the streaming
+ * CRC, {@code ozone.checksum.hip.batch.min.bytes} for the CRC batch, {@code ozone.checksum.hip.digest.min.bytes} for the
+ * SHA256 / MD5 batch), {@link #isAvailable} is false or the provider is never
  * found, and Checksum / ChecksumByteBufferFactory run the reference's code unchanged.
  */
 public final class HipChecksumAccelerator implements ChecksumAccelerator {
@@ -21,8 +22,8 @@ public final class HipChecksumAccelerator implements ChecksumAccelerator {
 
   @Override
   public boolean isAvailable() {
-    return (HipChecksumByteBuffer.MIN_GPU_BYTES != Integer.MAX_VALUE || HipChecksum.MIN_GPU_BYTES != Long.MAX_VALUE)
-        && OzecNative.isAvailable();
+    return (HipChecksumByteBuffer.MIN_GPU_BYTES != Integer.MAX_VALUE || HipChecksum.MIN_GPU_BYTES != Long.MAX_VALUE
+        || HipChecksum.MIN_GPU_DIGEST_BYTES != Long.MAX_VALUE) && OzecNative.isAvailable();
   }
 
   @Override

@@ -23,6 +23,8 @@ public final class OzecNative {
   public static final int CHECKSUM_NONE = 1;
   public static final int CHECKSUM_CRC32 = 2;
   public static final int CHECKSUM_CRC32C = 3;
+  public static final int CHECKSUM_SHA256 = 4;
+  public static final int CHECKSUM_MD5 = 5;
 
   private static final Throwable LOAD_FAILURE;
 
@@ -129,6 +131,16 @@ public final class OzecNative {
       int bytesPerChecksum, byte[] out);
 
   public static native int checksumWindowsArray(int type, byte[] data, int offset, int length,
+      int bytesPerChecksum, byte[] out);
+
+  /**
+   * MessageDigest.digest() of every bytesPerChecksum window into out, for CHECKSUM_SHA256 (32 bytes per window) or
+   * CHECKSUM_MD5 (16) (ozec_digest_windows); returns the bytes written.
+   */
+  public static native int digestWindowsDirect(int type, ByteBuffer data, int offset, int length,
+      int bytesPerChecksum, byte[] out);
+
+  public static native int digestWindowsArray(int type, byte[] data, int offset, int length,
       int bytesPerChecksum, byte[] out);
 
   // ---- pinned host memory + stripe queue (ozec_host_alloc, ozec_stripe_queue_*)

@@ -640,7 +640,10 @@ JNIEXPORT jint JNICALL JNI_FN(crcUpdateArray)(JNIEnv *env, jclass cls, jint type
  * of whole windows): big-endian CRC bytes of every window into out (SetByteArrayRegion, no pin across the GPU call);
  * returns the number of bytes written (4 per window) */
 static jint checksum_windows(JNIEnv *env, jint type, jobject direct, jbyteArray data, jint off, jint len, jint bpc,
-                             jbyteArray out) {
+                             jbyteArray out, int digest) {
+  /* bytes per window: 4 (CRC types), or the digest length (digestWindows*: 32 / 16; 0 for a type that is neither SHA256
+   * nor MD5, which ozm_digest_windows refuses below before anything else is looked at) */
+  const int64_t wb = digest ? (int64_t)ozec_digest_length(type) : 4;
   ozm_status st;
   if (!out) {
     ozm_fail(OZEC_EINVAL, "null checksum output", &st);
@@ -661,9 +664,10 @@ static jint checksum_windows(JNIEnv *env, jint type, jobject direct, jbyteArray 
   int rc = 0;
   int64_t total = 0;
   const uint8_t *unused;
-  if (bpc <= 0) rc = ozm_fail(OZEC_EINVAL, "bytesPerChecksum must be positive", &st);
+  if (wb == 0) rc = ozm_digest_windows(type, &b, 0, 1, NULL, 0, NULL, &st);
+  else if (bpc <= 0) rc = ozm_fail(OZEC_EINVAL, "bytesPerChecksum must be positive", &st);
   else if (len != 0 && (rc = ozm_resolve(&b, 1, 0, len, &unused, &st)) == 0 &&
-           (int64_t)cap < 4 * (((int64_t)len + bpc - 1) / bpc))
+           (int64_t)cap < wb * (((int64_t)len + bpc - 1) / bpc))
     rc = ozm_fail(OZEC_EINVAL, "checksum output too small", &st);
   /* whole windows per round trip (at least one): the arena holds the chunk's data (byte[] only) and its CRCs */
   const int64_t chunk = bpc <= 0 ? 1 : HEAP_CHUNK < bpc ? bpc : HEAP_CHUNK / bpc * bpc;
@@ -672,7 +676,7 @@ static jint checksum_windows(JNIEnv *env, jint type, jobject direct, jbyteArray 
   for (int64_t o = 0; !rc && o < len; o += chunk) {
     const int64_t cl = len - o < chunk ? len - o : chunk;
     const int64_t nw = (cl + bpc - 1) / bpc, dbytes = direct ? 0 : round_up(cl, ARENA_ALIGN);
-    uint8_t *a = arena(&l, (size_t)(dbytes + 4 * nw), &st);
+    uint8_t *a = arena(&l, (size_t)(dbytes + wb * nw), &st);
     if (!a) {
       rc = st.code;
       break;
@@ -687,7 +691,8 @@ static jint checksum_windows(JNIEnv *env, jint type, jobject direct, jbyteArray 
       c.offset = off + o;
     }
     int64_t written = 0;
-    rc = ozm_checksum_windows(type, &c, cl, bpc, a + dbytes, 4 * nw, &written, &st);
+    rc = digest ? ozm_digest_windows(type, &c, cl, bpc, a + dbytes, wb * nw, &written, &st)
+                : ozm_checksum_windows(type, &c, cl, bpc, a + dbytes, 4 * nw, &written, &st);
     if (!rc) {
       (*env)->SetByteArrayRegion(env, out, (jsize)total, (jsize)written, (const jbyte *)(a + dbytes));
       total += written;
@@ -701,13 +706,27 @@ static jint checksum_windows(JNIEnv *env, jint type, jobject direct, jbyteArray 
 JNIEXPORT jint JNICALL JNI_FN(checksumWindowsDirect)(JNIEnv *env, jclass cls, jint type, jobject buf, jint off, jint len,
                                                      jint bpc, jbyteArray out) {
   (void)cls;
-  return checksum_windows(env, type, buf, NULL, off, len, bpc, out);
+  return checksum_windows(env, type, buf, NULL, off, len, bpc, out, 0);
 }
 
 JNIEXPORT jint JNICALL JNI_FN(checksumWindowsArray)(JNIEnv *env, jclass cls, jint type, jbyteArray data, jint off,
                                                     jint len, jint bpc, jbyteArray out) {
   (void)cls;
-  return checksum_windows(env, type, NULL, data, off, len, bpc, out);
+  return checksum_windows(env, type, NULL, data, off, len, bpc, out, 0);
+}
+
+/* HipChecksum.computeChecksum for ChecksumType SHA256 / MD5 (MessageDigest per window, Checksum.java:43-57,76-81;
+ * ozec_digest_windows): the same two forms, `out` a byte[] of windows * digest length; returns the bytes written */
+JNIEXPORT jint JNICALL JNI_FN(digestWindowsDirect)(JNIEnv *env, jclass cls, jint type, jobject buf, jint off, jint len,
+                                                   jint bpc, jbyteArray out) {
+  (void)cls;
+  return checksum_windows(env, type, buf, NULL, off, len, bpc, out, 1);
+}
+
+JNIEXPORT jint JNICALL JNI_FN(digestWindowsArray)(JNIEnv *env, jclass cls, jint type, jbyteArray data, jint off,
+                                                  jint len, jint bpc, jbyteArray out) {
+  (void)cls;
+  return checksum_windows(env, type, NULL, data, off, len, bpc, out, 1);
 }
 
 /* ---------------------------------------------------------------- pinned memory + stripe queue (§8(f) row 3) */

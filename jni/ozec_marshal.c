@@ -145,6 +145,24 @@ int ozm_checksum_windows(int checksum_type, const ozm_buf *buf, int64_t len, int
   return ok(st);
 }
 
+int ozm_digest_windows(int checksum_type, const ozm_buf *buf, int64_t len, int64_t bpc, uint8_t *out, int64_t out_cap,
+                       int64_t *written, ozm_status *st) {
+  const uint8_t *p = NULL;
+  if (written) *written = 0;
+  const int64_t dl = (int64_t)ozec_digest_length(checksum_type);
+  if (dl == 0) return ozm_fail(ozec_digest_windows(checksum_type, NULL, 0, 1, NULL), NULL, st); /* libozec's message */
+  if (bpc <= 0) return ozm_fail(OZEC_EINVAL, "bytesPerChecksum must be positive", st);
+  if (len == 0) return ok(st); /* empty data: an empty checksum list (Checksum.java:171-178) */
+  const int64_t nwin = (len + bpc - 1) / bpc;
+  if (!out || out_cap < dl * nwin) return ozm_fail(OZEC_EINVAL, "checksum output too small", st);
+  if (ozm_resolve(buf, 1, 0, len, &p, st)) return st ? st->code : OZEC_EINVAL;
+  /* the bytes of MessageDigest.digest() per window, as Checksum.java:76-81 wraps them */
+  int rc = ozec_digest_windows(checksum_type, p, (size_t)len, (size_t)bpc, out);
+  if (rc) return ozm_fail(rc, NULL, st);
+  if (written) *written = dl * nwin;
+  return ok(st);
+}
+
 /* bytes a buffer must hold from its offset, or fail */
 static int need(const ozm_buf *b, int64_t bytes, const char *what, const uint8_t **out, ozm_status *st) {
   char msg[128];

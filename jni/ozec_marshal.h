@@ -77,6 +77,10 @@ int ozm_crc_update(int checksum_type, uint32_t *state, const ozm_buf *buf, int64
  * bytes_per_checksum window into out (out_cap bytes, >= 4 * ceil(len / bpc)); *written = bytes stored */
 int ozm_checksum_windows(int checksum_type, const ozm_buf *buf, int64_t len, int64_t bytes_per_checksum,
                          uint8_t *out, int64_t out_cap, int64_t *written, ozm_status *st);
+/* the same for ChecksumType SHA256 / MD5 (ozec_digest_windows): ozec_digest_length(type) bytes per window, the bytes of
+ * MessageDigest.digest() (Checksum.java:76-81); any other type fails with libozec's message */
+int ozm_digest_windows(int checksum_type, const ozm_buf *buf, int64_t len, int64_t bytes_per_checksum, uint8_t *out,
+                       int64_t out_cap, int64_t *written, ozm_status *st);
 
 /* Batch reconstruction of stripes held in direct buffers (ECReconstructionCoordinator's read buffers; libozec
  * ozec_reconstruct_crc_host_batch).  stripes: [S][k+p][cell_len] at stripe_stride / unit_stride (absent and erased

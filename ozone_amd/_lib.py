@@ -27,6 +27,8 @@ OZEC_CODEC_XOR = 1
 OZEC_CHECKSUM_NONE = 1
 OZEC_CHECKSUM_CRC32 = 2
 OZEC_CHECKSUM_CRC32C = 3
+OZEC_CHECKSUM_SHA256 = 4
+OZEC_CHECKSUM_MD5 = 5
 OZEC_MAX_K = 64
 OZEC_MAX_ROWS = 16
 OP_NAMES = ["encode", "decode", "encode_device", "decode_device", "fused", "host_batch", "checksum",
@@ -97,6 +99,13 @@ _SIGS = {
                                             ctypes.POINTER(c_i64)]),
     "ozec_checksum_verify_batch": (ctypes.c_int, [ctypes.c_int, c_voidp, c_i64, c_size, c_size, c_size, c_voidp,
                                                   ctypes.c_int, c_voidp, c_voidp]),
+    "ozec_digest_length": (c_size, [ctypes.c_int]),
+    "ozec_digest_windows": (ctypes.c_int, [ctypes.c_int, c_voidp, c_size, c_size, c_voidp]),
+    "ozec_digest_windows_device": (ctypes.c_int, [ctypes.c_int, c_voidp, c_size, c_size, c_voidp, c_voidp]),
+    "ozec_digest_windows_batch": (ctypes.c_int, [ctypes.c_int, c_voidp, c_i64, c_size, c_size, c_size, c_voidp,
+                                                 c_voidp]),
+    "ozec_digest_verify_batch": (ctypes.c_int, [ctypes.c_int, c_voidp, c_i64, c_size, c_size, c_size, c_voidp,
+                                                c_voidp, c_voidp]),
     "ozec_reconstruct_crc_batch": (ctypes.c_int, [c_voidp, c_voidp, c_i64, c_i64, c_intp, ctypes.c_int, c_intp,
                                                   ctypes.c_int, c_voidp, c_i64, c_i64, c_size, c_size, ctypes.c_int,
                                                   c_size, c_voidp, ctypes.c_int, c_voidp, ctypes.c_int, c_voidp,

@@ -7,8 +7,9 @@ Mirrors hadoop-hdds/common (CM/ = .../org/apache/hadoop/ozone/common/):
   ChecksumType {NONE=1, CRC32=2, CRC32C=3, SHA256=4, MD5=5}  DatanodeClientProtocol.proto:422-434
 CRC32/CRC32C windows are computed by libozec.so on the GPU (one CRC per bytesPerChecksum window, last window
 short, stored as the 4 big-endian bytes of (int)getValue() -- Checksum.int2ByteString, Checksum.java:59-70).
-SHA256/MD5 are outside the GPU scope of this build (BASELINE.json north_star names CRC32/CRC32C); they are
-delegated to hashlib exactly as the reference delegates them to MessageDigest (Checksum.java:42-57).
+SHA256/MD5 windows (MessageDigest per window in the reference, Checksum.java:42-57,76-81) are computed on the GPU
+too, one lane per window (ozec_digest_windows; digest_windows below), whenever libozec sees a device; a process
+with no GPU computes them with hashlib, the same bytes.
 """
 import ctypes
 import enum
@@ -69,6 +70,18 @@ def crc_windows(checksum_type, data, bytes_per_checksum):
     return out[:nwin]
 
 
+def digest_windows(checksum_type, data, bytes_per_checksum):
+    """list of bytes, one MessageDigest.digest() per window (SHA256: 32 bytes, MD5: 16), computed on the GPU."""
+    a = _as_u8(data)
+    dl = L.lib().ozec_digest_length(int(checksum_type))
+    nwin = (a.size + bytes_per_checksum - 1) // bytes_per_checksum if bytes_per_checksum > 0 else 0
+    out = np.zeros(max(1, nwin * dl), np.uint8)
+    rc = L.lib().ozec_digest_windows(int(checksum_type), a.ctypes.data, a.size, bytes_per_checksum, out.ctypes.data)
+    if rc != L.OZEC_OK:
+        raise OzoneChecksumException(L.last_error())
+    return [out[i * dl:(i + 1) * dl].tobytes() for i in range(nwin)]
+
+
 class ChecksumData:
     """ChecksumData (CM/ChecksumData.java:35-193)."""
 
@@ -126,7 +139,9 @@ class Checksum:
         if self.checksum_type in (ChecksumType.CRC32, ChecksumType.CRC32C):
             vals = crc_windows(self.checksum_type, a, bpc)
             return ChecksumData(self.checksum_type, bpc, [int2bytes(v) for v in vals])
-        algo = "sha256" if self.checksum_type == ChecksumType.SHA256 else "md5"
+        if L.lib().ozec_device_count() > 0:
+            return ChecksumData(self.checksum_type, bpc, digest_windows(self.checksum_type, a, bpc))
+        algo = "sha256" if self.checksum_type == ChecksumType.SHA256 else "md5"  # no GPU in this process
         sums = [hashlib.new(algo, a[o:o + bpc].tobytes()).digest() for o in range(0, a.size, bpc)]
         return ChecksumData(self.checksum_type, bpc, sums)
 
@@ -199,6 +214,24 @@ def checksum_verify_batch(checksum_type, d_base, cell_stride, num_cells, length,
     rc = L.lib().ozec_checksum_verify_batch(int(checksum_type), _dev_ptr(d_base), cell_stride, num_cells, length,
                                             bytes_per_checksum, _dev_ptr(d_expected), 1 if expected_big_endian else 0,
                                             _dev_ptr(d_mismatch), _stream_ptr(stream))
+    if rc != L.OZEC_OK:
+        raise OzoneChecksumException(L.last_error())
+
+
+def digest_windows_batch(checksum_type, d_base, cell_stride, num_cells, length, bytes_per_checksum, d_out, stream=None):
+    """Device-resident batch of SHA256 / MD5 windows: digests to d_out[c][w][digest_len] (uint8, dense)."""
+    rc = L.lib().ozec_digest_windows_batch(int(checksum_type), _dev_ptr(d_base), cell_stride, num_cells, length,
+                                           bytes_per_checksum, _dev_ptr(d_out), _stream_ptr(stream))
+    if rc != L.OZEC_OK:
+        raise OzoneChecksumException(L.last_error())
+
+
+def digest_verify_batch(checksum_type, d_base, cell_stride, num_cells, length, bytes_per_checksum, d_expected,
+                        d_mismatch, stream=None):
+    """checksum_verify_batch for SHA256 / MD5: d_expected[c][w][digest_len], d_mismatch[c] = -1 or first failing window."""
+    rc = L.lib().ozec_digest_verify_batch(int(checksum_type), _dev_ptr(d_base), cell_stride, num_cells, length,
+                                          bytes_per_checksum, _dev_ptr(d_expected), _dev_ptr(d_mismatch),
+                                          _stream_ptr(stream))
     if rc != L.OZEC_OK:
         raise OzoneChecksumException(L.last_error())
 

@@ -22,6 +22,8 @@
 #include "../../include/ozec.h"
 #include "crc_host.hpp"
 #include "devices.hpp"
+#include "digest.hpp"
+#include "digest_core.hpp"
 #include "gf256.hpp"
 #include "copy_pool.hpp"
 #include "kernels.hpp"
@@ -1621,6 +1623,110 @@ int ozec_checksum_verify_batch(int checksum_type, const uint8_t *d_base, int64_t
   }
   OZEC_HIP(ozec::launch_finish_mismatch(d_mismatch, static_cast<int64_t>(num_cells), st));
   return OZEC_OK;
+}
+
+// ---- SHA256 / MD5 window digests (Checksum.java:43-57,76-81: MessageDigest per bytesPerChecksum window) ----------
+
+namespace {
+
+// argument checks shared by the digest entry points, all before any device is touched; *algo = digest::Algo
+int digest_algo_of(int checksum_type, size_t bpc, int *algo) {
+  if (checksum_type == OZEC_CHECKSUM_SHA256) *algo = ozec::digest::kSha256;
+  else if (checksum_type == OZEC_CHECKSUM_MD5) *algo = ozec::digest::kMd5;
+  else return fail(OZEC_EINVAL, "unsupported digest type " + std::to_string(checksum_type) +
+                                    " (SHA256=4 and MD5=5; the CRC types go through ozec_checksum_windows)");
+  if (bpc == 0) return fail(OZEC_EINVAL, "bytesPerChecksum must be positive");
+  return OZEC_OK;
+}
+
+int make_digest_args(const uint8_t *d_base, int64_t cell_stride, size_t ncells, size_t len, size_t bpc,
+                     ozec::DigestArgs *a) {
+  const size_t nwin = (len + bpc - 1) / bpc;
+  if (nwin > static_cast<size_t>(INT32_MAX)) return fail(OZEC_EINVAL, "more than 2^31 - 1 windows per cell");
+  if (ncells > 1 && cell_stride < static_cast<int64_t>(len)) return fail(OZEC_EINVAL, "cell_stride < len");
+  *a = ozec::DigestArgs{};
+  a->base = d_base;
+  a->cell_stride = cell_stride;
+  a->ncells = static_cast<int64_t>(ncells);
+  a->len = static_cast<int64_t>(len);
+  a->bpc = static_cast<int64_t>(bpc);
+  a->nwin = static_cast<int64_t>(nwin);
+  return OZEC_OK;
+}
+
+}  // namespace
+
+size_t ozec_digest_length(int checksum_type) {
+  return checksum_type == OZEC_CHECKSUM_SHA256 ? 32 : checksum_type == OZEC_CHECKSUM_MD5 ? 16 : 0;
+}
+
+int ozec_digest_windows_batch(int checksum_type, const uint8_t *d_base, int64_t cell_stride, size_t num_cells, size_t len,
+                              size_t bpc, uint8_t *d_out, void *stream) {
+  ozec::StatScope stat_(OZEC_OP_CHECKSUM_DEVICE, static_cast<uint64_t>(len) * num_cells);
+  int algo;
+  if (int rc = digest_algo_of(checksum_type, bpc, &algo)) return rc;
+  if (len == 0 || num_cells == 0) return OZEC_OK;
+  if (!d_base || !d_out) return fail(OZEC_EINVAL, "null buffer");
+  ozec::DigestArgs a;
+  if (int rc = make_digest_args(d_base, cell_stride, num_cells, len, bpc, &a)) return rc;
+  a.out = d_out;
+  DevCtx *ctx;
+  if (int rc = get_ctx(&ctx)) return rc;
+  OZEC_HIP(ozec::launch_digest_windows(algo, a, pick_stream(ctx, stream)));
+  return OZEC_OK;
+}
+
+int ozec_digest_windows_device(int checksum_type, const uint8_t *d_data, size_t len, size_t bpc, uint8_t *d_out,
+                               void *stream) {
+  return ozec_digest_windows_batch(checksum_type, d_data, 0, 1, len, bpc, d_out, stream);
+}
+
+int ozec_digest_verify_batch(int checksum_type, const uint8_t *d_base, int64_t cell_stride, size_t num_cells, size_t len,
+                             size_t bpc, const uint8_t *d_expected, int32_t *d_mismatch, void *stream) {
+  ozec::StatScope stat_(OZEC_OP_CHECKSUM_DEVICE, static_cast<uint64_t>(len) * num_cells);
+  int algo;
+  if (int rc = digest_algo_of(checksum_type, bpc, &algo)) return rc;
+  if (len == 0 || num_cells == 0) return OZEC_OK;
+  if (!d_base || !d_expected || !d_mismatch) return fail(OZEC_EINVAL, "null buffer");
+  ozec::DigestArgs a;
+  if (int rc = make_digest_args(d_base, cell_stride, num_cells, len, bpc, &a)) return rc;
+  a.expected = d_expected;
+  a.mismatch = d_mismatch;
+  DevCtx *ctx;
+  if (int rc = get_ctx(&ctx)) return rc;
+  hipStream_t st = pick_stream(ctx, stream);
+  // the initialise / finish steps of ozec_checksum_verify_batch: INT32_MAX, atomicMin of the failing windows, then -1
+  OZEC_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_mismatch), 0x7fffffff, num_cells, st));
+  OZEC_HIP(ozec::launch_digest_windows(algo, a, st));
+  OZEC_HIP(ozec::launch_finish_mismatch(d_mismatch, static_cast<int64_t>(num_cells), st));
+  return OZEC_OK;
+}
+
+// host buffers through the staging pipeline, as checksum_host: chunks are whole windows, every chunk's digests are
+// the call's digests
+int ozec_digest_windows(int checksum_type, const uint8_t *data, size_t len, size_t bpc, uint8_t *out) {
+  ozec::StatScope stat_(OZEC_OP_CHECKSUM, len);
+  int algo;
+  if (int rc = digest_algo_of(checksum_type, bpc, &algo)) return rc;
+  if (len == 0) return OZEC_OK;
+  if (!data || !out) return fail(OZEC_EINVAL, "null buffer");
+  if ((len + bpc - 1) / bpc > static_cast<size_t>(INT32_MAX)) return fail(OZEC_EINVAL, "more than 2^31 - 1 windows");
+  ozec::DeviceScope ds(ozec::thread_device());  // coder-less host call: this thread's GPU (devices.hpp)
+  if (!ds.ok()) return fail(OZEC_EDEVICE, "cannot select this thread's device");
+  DevCtx *ctx;
+  if (int rc = get_ctx(&ctx)) return rc;
+  const size_t dl = ozec_digest_length(checksum_type);
+  uint8_t *outs[1] = {out};
+  const size_t gran = bpc >= 4096 ? bpc : (4096 + bpc - 1) / bpc * bpc;
+  return staged_pipeline(
+      ctx, 1, &data, len, gran, 1, outs, [bpc, dl](size_t cl) { return (cl + bpc - 1) / bpc * dl; },
+      [bpc, dl](size_t off) { return off / bpc * dl; },
+      [&](uint8_t *d_in, int64_t, uint8_t *d_out, int64_t, size_t, size_t cl, hipStream_t st) {
+        ozec::DigestArgs a;
+        if (make_digest_args(d_in, 0, 1, cl, bpc, &a)) return hipErrorInvalidValue;
+        a.out = d_out;
+        return ozec::launch_digest_windows(algo, a, st);
+      });
 }
 
 int ozec_reconstruct_crc_batch(ozec_coder *dec, const uint8_t *d_in, int64_t in_stripe_stride, int64_t in_unit_stride,
