@@ -46,7 +46,11 @@ extern "C" {
 #define OZEC_CHECKSUM_NONE 1
 #define OZEC_CHECKSUM_CRC32 2
 #define OZEC_CHECKSUM_CRC32C 3
-#define OZEC_CHECKSUM_SHA256 4    /* window digests: ozec_digest_* below; every other entry point takes the CRC types only */
+/* SHA256 / MD5 window digests: the stand-alone calls ozec_digest_*, and the stripe paths' digest forms --
+ * ozec_encode_digest_batch, ozec_reconstruct_digest_batch, their _host_batch forms and a stripe queue created with one
+ * of these types (ozec_stripe_queue_submit_digests).  The CRC-typed entry points (_crc_, ozec_checksum_*) take the CRC
+ * types only and answer OZEC_EINVAL for these two. */
+#define OZEC_CHECKSUM_SHA256 4
 #define OZEC_CHECKSUM_MD5 5
 
 #define OZEC_MAX_K 64             /* data units handled by the GPU kernels      */
@@ -274,6 +278,47 @@ int ozec_reconstruct_crc_host_batch(ozec_coder *dec, const uint8_t *h_in, int64_
                                     const uint32_t *h_expected, int expected_big_endian, uint32_t *h_out_crcs,
                                     int out_big_endian, int32_t *h_mismatch, size_t stripes_per_chunk);
 
+/* ---- stripes with SHA256 / MD5 window digests: what the writer and the reconstruction coordinator do when
+ *      ozone.client.checksum.type is SHA256 or MD5 (OzoneClientConfig.java:166, CM/Checksum.java:80-81): the calls
+ *      above with digests (ozec_digest_length() bytes per window, the bytes of MessageDigest.digest(), no endian flag)
+ *      where those have uint32 CRCs.  Each runs the coding launch and then ONE digest launch over every unit of every
+ *      stripe, one lane per window: a digest launch lasts at least one lane's walk over one window whatever the batch,
+ *      so few launches matter for small batches, and windows of tens of KiB keep the host forms link-bound while 1 MiB
+ *      windows leave a 32-stripe chunk bound by a few hundred lanes' serial hashing.
+ *      checksum_type must be OZEC_CHECKSUM_SHA256 / _MD5 (CRC types and NONE: the _crc_ counterpart) and
+ *      bytes_per_checksum positive; every argument error is reported before a device is touched; len == 0 or
+ *      num_stripes == 0 is OZEC_OK and writes nothing, except that ozec_reconstruct_digest_* with len == 0 still sets
+ *      d_mismatch[s] = -1. ---- */
+/* ozec_encode_batch (same parity, XOR's zero-filled outputs included), then d_digests[s][u][w][digest_len], dense, for
+ * u over the k data units and then the coded parity rows (XOR: one) */
+int ozec_encode_digest_batch(ozec_coder *enc, const uint8_t *d_in, int64_t in_stripe_stride, int64_t in_unit_stride,
+                             uint8_t *d_out, int64_t out_stripe_stride, int64_t out_unit_stride, size_t num_stripes,
+                             size_t len, int checksum_type, size_t bytes_per_checksum, uint8_t *d_digests,
+                             void *stream);
+/* ozec_reconstruct_crc_batch with digests: d_expected[s][k+p][w][digest_len] (NULL = skip verification; only the k units
+ * the decoder reads are checked, the other units' entries are never read), d_out_digests[s][num_erased][w][digest_len]
+ * for every output (the XOR decoder's zero-filled ones included), d_mismatch[s] = -1 or the smallest
+ * unit * nwin + window whose digest did not verify.  Decodes, then one digest launch in which the read units' lanes
+ * verify and the rebuilt units' lanes compute.  OZEC_EINVAL when (k+p) * nwin does not fit an int32. */
+int ozec_reconstruct_digest_batch(ozec_coder *dec, const uint8_t *d_in, int64_t in_stripe_stride,
+                                  int64_t in_unit_stride, const int *present, int num_present, const int *erased,
+                                  int num_erased, uint8_t *d_out, int64_t out_stripe_stride, int64_t out_unit_stride,
+                                  size_t num_stripes, size_t len, int checksum_type, size_t bytes_per_checksum,
+                                  const uint8_t *d_expected, uint8_t *d_out_digests, int32_t *d_mismatch, void *stream);
+/* the two calls for stripes in HOST memory, through the chunk pipelines of ozec_encode_crc_host_batch /
+ * ozec_reconstruct_crc_host_batch (one coding and one digest launch per chunk; split over the device list likewise).
+ * Link-bound at bytes_per_checksum up to tens of KiB; at 1 MiB windows bound by the lanes' serial hashing. */
+int ozec_encode_digest_host_batch(ozec_coder *enc, const uint8_t *h_in, int64_t in_stripe_stride,
+                                  int64_t in_unit_stride, uint8_t *h_out, int64_t out_stripe_stride,
+                                  int64_t out_unit_stride, size_t num_stripes, size_t len, int checksum_type,
+                                  size_t bytes_per_checksum, uint8_t *h_digests, size_t stripes_per_chunk);
+int ozec_reconstruct_digest_host_batch(ozec_coder *dec, const uint8_t *h_in, int64_t in_stripe_stride,
+                                       int64_t in_unit_stride, const int *present, int num_present, const int *erased,
+                                       int num_erased, uint8_t *h_out, int64_t out_stripe_stride,
+                                       int64_t out_unit_stride, size_t num_stripes, size_t len, int checksum_type,
+                                       size_t bytes_per_checksum, const uint8_t *h_expected, uint8_t *h_out_digests,
+                                       int32_t *h_mismatch, size_t stripes_per_chunk);
+
 /* ---- streaming ChecksumByteBuffer (CM/ChecksumByteBuffer.java:32-44): update(ByteBuffer) / getValue /
  *      reset over an opaque 32-bit state.  The GPU computes the raw CRC of the buffer and the host combines
  *      it with the running state (x^(8n) mod P shift), so results equal the sequential CrcIntTable. ---- */
@@ -339,13 +384,20 @@ uint64_t ozec_host_placement_failures(void);
 int ozec_host_unregister(void *p);
 typedef struct ozec_stripe_queue ozec_stripe_queue;
 /* checksum_type OZEC_CHECKSUM_NONE: parity only; CRC32 / CRC32C: also the bpc-window CRCs of all k+p units,
- * written per stripe as crcs[unit][window] (window count from the stripe's length), big-endian if asked */
+ * written per stripe as crcs[unit][window] (window count from the stripe's length), big-endian if asked; SHA256 / MD5:
+ * the windows' digests instead, digests[unit][window][digest_len] (big_endian is ignored), for stripes submitted with
+ * ozec_stripe_queue_submit_digests */
 int ozec_stripe_queue_create(ozec_coder *encoder, size_t cell_len, size_t stripes_per_batch, int checksum_type,
                              size_t bpc, int big_endian, ozec_stripe_queue **out);
 /* queue one stripe (k data cells of len <= cell_len bytes -> p parity cells, optional CRCs); a batch holds one
  * length, so a stripe of another length first launches the pending batch.  *ticket identifies the stripe. */
 int ozec_stripe_queue_submit(ozec_stripe_queue *q, const uint8_t *const *data, uint8_t *const *parity, size_t len,
                              uint32_t *crcs, uint64_t *ticket);
+/* the same for a queue created with SHA256 / MD5: digests[unit][window][digest_len] for the stripe's own window count
+ * (NULL: parity only).  OZEC_EINVAL on a CRC or NONE queue, as ozec_stripe_queue_submit with non-null crcs is on a
+ * digest queue. */
+int ozec_stripe_queue_submit_digests(ozec_stripe_queue *q, const uint8_t *const *data, uint8_t *const *parity, size_t len,
+                                     uint8_t *digests, uint64_t *ticket);
 /* launch the partly filled batch now */
 int ozec_stripe_queue_flush(ozec_stripe_queue *q);
 /* block until every stripe up to and including `ticket` has its parity (and CRCs) in the caller's buffers */
@@ -401,11 +453,11 @@ int ozec_crc_compose_windows_batch(int checksum_type, const uint32_t *d_crcs, in
 #define OZEC_OP_DECODE 1          /* ozec_decode                                                            */
 #define OZEC_OP_ENCODE_DEVICE 2   /* ozec_encode_device / ozec_encode_batch                                 */
 #define OZEC_OP_DECODE_DEVICE 3   /* ozec_decode_device / ozec_decode_batch                                 */
-#define OZEC_OP_FUSED 4           /* ozec_encode_crc_batch / _block_groups / ozec_reconstruct_crc_batch      */
-#define OZEC_OP_HOST_BATCH 5      /* ozec_encode_crc_host_batch / ozec_reconstruct_crc_host_batch           */
+#define OZEC_OP_FUSED 4           /* ozec_encode_crc_batch / _block_groups / ozec_reconstruct_crc_batch, ozec_encode_digest_batch / ozec_reconstruct_digest_batch */
+#define OZEC_OP_HOST_BATCH 5      /* ozec_encode_crc_host_batch / ozec_reconstruct_crc_host_batch and their _digest_ forms */
 #define OZEC_OP_CHECKSUM 6        /* ozec_checksum_windows / _verify / ozec_crc_update / ozec_digest_windows (host buffers) */
 #define OZEC_OP_CHECKSUM_DEVICE 7 /* ozec_checksum_windows_batch / _device / ozec_checksum_verify_batch, ozec_digest_*_batch / _device */
-#define OZEC_OP_QUEUE 8           /* ozec_stripe_queue_submit / _flush / _wait                              */
+#define OZEC_OP_QUEUE 8           /* ozec_stripe_queue_submit / _submit_digests / _flush / _wait            */
 #define OZEC_NUM_OPS 9
 typedef struct {
   uint64_t calls;

@@ -68,7 +68,10 @@ abstract class AbstractHipRawDecoder extends RawErasureDecoder {
    * stripes [numStripes][k+p][cellLength] at stripeStride / unitStride; out [numStripes][erased][cellLength];
    * outChecksums [numStripes][erased][windows] and expectedChecksums [numStripes][k+p][windows] as 4-byte big-endian
    * values (the ByteStrings of ChecksumData); mismatch [numStripes] native-order ints, -1 or the first failing
-   * unit * windows + window.  expectedChecksums and mismatch may be null (no verification).
+   * unit * windows + window.  expectedChecksums and mismatch may be null (no verification).  With ChecksumType SHA256
+   * (4) or MD5 (5) the two checksum buffers hold the windows' digests (ozec_reconstruct_digest_host_batch), the bytes
+   * of MessageDigest.digest(): outChecksums [numStripes][erased][windows][digestLength] and expectedChecksums
+   * [numStripes][k+p][windows][digestLength], digestLength 32 or 16; their capacities are checked with that size.
    */
   public void reconstructBatch(ByteBuffer stripes, long stripeStride, long unitStride, int[] presentUnits,
       int[] erasedIndexes, ByteBuffer out, int numStripes, int cellLength, int checksumType, int bytesPerChecksum,

@@ -22,7 +22,9 @@ public final class HipStripeQueue implements AutoCloseable {
 
   /**
    * @param checksumType OzecNative.CHECKSUM_NONE / CHECKSUM_CRC32 / CHECKSUM_CRC32C; CRCs are written big-endian,
-   *                     i.e. the bytes Checksum.int2ByteString stores (Checksum.java:59-70)
+   *                     i.e. the bytes Checksum.int2ByteString stores (Checksum.java:59-70).  ChecksumType SHA256 (4)
+   *                     and MD5 (5) give the windows' digests instead: the bytes of MessageDigest.digest(), 32 or 16
+   *                     per window (Checksum.java:76-81)
    */
   public HipStripeQueue(RawErasureEncoder encoder, int cellSize, int stripesPerBatch, int checksumType,
       int bytesPerChecksum) {
@@ -35,7 +37,12 @@ public final class HipStripeQueue implements AutoCloseable {
         checksumType, bytesPerChecksum);
   }
 
-  /** Queue one stripe; returns its ticket.  crcs (direct, may be null) receives (k + coded parity) x windows CRCs. */
+  /**
+   * Queue one stripe; returns its ticket.  crcs (direct, may be null) receives, from its position, the checksums of
+   * the k data cells and then the coded parity cells: [unit][window] 4-byte big-endian CRCs on a CRC queue,
+   * [unit][window][digest length] digest bytes on a SHA256 / MD5 queue; windows = ceil(length / bytesPerChecksum).
+   * A buffer with less room than that is refused with HadoopIllegalArgumentException before anything is queued.
+   */
   public synchronized long submit(ByteBuffer[] dataCells, ByteBuffer[] parityCells, int length, ByteBuffer crcs)
       throws IOException {
     if (queue == 0) {

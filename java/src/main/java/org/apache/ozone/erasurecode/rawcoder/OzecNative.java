@@ -148,6 +148,8 @@ public final class OzecNative {
 
   public static native void freePinned(ByteBuffer buffer);
 
+  // checksumType 4 / 5 (SHA256 / MD5): queueSubmit's crcs buffer receives [unit][window][digest length] digest bytes
+  // (ozec_stripe_queue_submit_digests) and needs units * windows * digest length bytes of room from crcsOffset
   static native long queueCreate(long encoder, int cellLen, int stripesPerBatch, int checksumType,
       int bytesPerChecksum);
 
@@ -158,7 +160,9 @@ public final class OzecNative {
 
   static native void queueFree(long queue);
 
-  // ---- batch reconstruction from host buffers (ozec_reconstruct_crc_host_batch, SURVEY §8(f) row 1)
+  // ---- batch reconstruction from host buffers (ozec_reconstruct_crc_host_batch, SURVEY §8(f) row 1; checksumType
+  //      4 / 5 = SHA256 / MD5: ozec_reconstruct_digest_host_batch, expectedChecksums [stripe][k+p][window][digest length]
+  //      and outChecksums [stripe][erased][window][digest length])
   static native void reconstructHostBatch(long decoder, ByteBuffer stripes, long stripeStride, long unitStride,
       int[] presentUnits, int[] erasedIndexes, ByteBuffer out, int numStripes, int cellLength, int checksumType,
       int bytesPerChecksum, ByteBuffer expectedChecksums, ByteBuffer outChecksums, ByteBuffer mismatch);

@@ -767,7 +767,9 @@ JNIEXPORT jlong JNICALL JNI_FN(queueCreate)(JNIEnv *env, jclass cls, jlong enc, 
 
 /* submit(data cells, parity cells, len, crcs): direct buffers at their positions; returns the stripe's ticket.
  * The Java side keeps the buffers referenced until waitFor(ticket) returns (HipStripeQueue).  Cell counts, lengths
- * and the CRC buffer's room from crcsOffset are checked against the queue by ozm_queue_submit. */
+ * and the CRC buffer's room from crcsOffset are checked against the queue by ozm_queue_submit.  On a queue created
+ * with ChecksumType SHA256 / MD5 `crcs` receives digests, [unit][window][digest length], and its room is checked with
+ * the digest length (ozec_stripe_queue_submit_digests). */
 JNIEXPORT jlong JNICALL JNI_FN(queueSubmit)(JNIEnv *env, jclass cls, jlong q, jobjectArray data, jintArray dataOff,
                                             jobjectArray parity, jintArray parityOff, jint len, jobject crcs,
                                             jint crcsOffset) {
@@ -824,7 +826,8 @@ static ozm_buf direct_buf(JNIEnv *env, jobject b) {
 
 /* reconstructHostBatch(decoder, stripes, stripeStride, unitStride, present[], erased[], out, numStripes, cellLen,
  * checksumType, bytesPerChecksum, expected, outCrcs, mismatch): every buffer direct (allocatePinned for DMA in
- * place); CRC buffers hold big-endian ints as ChecksumData's ByteStrings do. */
+ * place); CRC buffers hold big-endian ints as ChecksumData's ByteStrings do, and for checksumType SHA256 / MD5 the
+ * windows' digests, [.][unit][window][digest length] (ozec_reconstruct_digest_host_batch). */
 JNIEXPORT void JNICALL JNI_FN(reconstructHostBatch)(JNIEnv *env, jclass cls, jlong dec, jobject stripes,
                                                     jlong stripeStride, jlong unitStride, jintArray present,
                                                     jintArray erased, jobject out, jint numStripes, jint cellLen,

@@ -204,13 +204,16 @@ int ozm_queue_submit(ozec_stripe_queue *q, const ozm_buf *data, int nd, const oz
   const uint8_t *dp[OZEC_MAX_K], *pp[256], *cp = NULL;
   if (k > OZEC_MAX_K || p > 256) return ozm_fail(OZEC_EUNSUPPORTED, "schema exceeds the kernel limits", st);
   if (ozm_resolve(data, nd, 0, len, dp, st) || ozm_resolve(parity, np, 0, len, pp, st)) return st ? st->code : OZEC_EINVAL;
+  /* bytes per window: 4 (a big-endian CRC), or the digest length of a SHA256 / MD5 queue */
+  const int64_t dl = (int64_t)ozec_digest_length(ctype), esz = dl ? dl : 4;
   if (ctype != OZEC_CHECKSUM_NONE && crcs && crcs->present) {
     const int64_t nwin = ((int64_t)len + (int64_t)bpc - 1) / (int64_t)bpc;
     int64_t bytes;
-    if (!span((int64_t)(k + rows) * nwin, 4, 0, &bytes)) return ozm_fail(OZEC_EINVAL, "checksum size overflows", st);
+    if (!span((int64_t)(k + rows) * nwin, esz, 0, &bytes)) return ozm_fail(OZEC_EINVAL, "checksum size overflows", st);
     if (need(crcs, bytes, "checksum", &cp, st)) return st ? st->code : OZEC_EINVAL;
   }
-  rc = ozec_stripe_queue_submit(q, dp, (uint8_t *const *)pp, (size_t)len, (uint32_t *)cp, ticket);
+  if (dl) rc = ozec_stripe_queue_submit_digests(q, dp, (uint8_t *const *)pp, (size_t)len, (uint8_t *)cp, ticket);
+  else rc = ozec_stripe_queue_submit(q, dp, (uint8_t *const *)pp, (size_t)len, (uint32_t *)cp, ticket);
   return rc ? ozm_fail(rc, NULL, st) : ok(st);
 }
 
@@ -229,14 +232,16 @@ int ozm_reconstruct_host_batch(ozec_coder *dec, const ozm_buf *stripes, int64_t 
   if (nerased > p) return ozm_fail(OZEC_EINVAL, "Too many erased, not recoverable", st);
   if (num_stripes == 0 || cell_len == 0) return ok(st);
   const int64_t nwin = (cell_len + bpc - 1) / bpc, S = num_stripes;
+  /* bytes per window: 4 (a big-endian CRC), or the digest length for SHA256 / MD5 */
+  const int64_t dl = (int64_t)ozec_digest_length(checksum_type), esz = dl ? dl : 4;
   const uint8_t *in = NULL, *o = NULL, *oc = NULL, *ex = NULL, *mm = NULL;
   /* every layout size in checked arithmetic: a huge Java stride must not wrap past the capacity check */
   int64_t last_unit, in_bytes, out_bytes, crc_bytes, exp_bytes, ner_cells, ner_crcs, units_crcs, out_stride;
   if (!span((int64_t)(k + p - 1), unit_stride, cell_len, &last_unit) ||
       !span(S - 1, stripe_stride, last_unit, &in_bytes) || !span(S, nerased, 0, &ner_cells) ||
       !span(ner_cells, cell_len, 0, &out_bytes) || !span(ner_cells, nwin, 0, &ner_crcs) ||
-      !span(ner_crcs, 4, 0, &crc_bytes) || !span(S, (int64_t)(k + p) * nwin, 0, &units_crcs) ||
-      !span(units_crcs, 4, 0, &exp_bytes) || !span(nerased, cell_len, 0, &out_stride))
+      !span(ner_crcs, esz, 0, &crc_bytes) || !span(S, (int64_t)(k + p) * nwin, 0, &units_crcs) ||
+      !span(units_crcs, esz, 0, &exp_bytes) || !span(nerased, cell_len, 0, &out_stride))
     return ozm_fail(OZEC_EINVAL, "buffer layout size overflows", st);
   if (need(stripes, in_bytes, "stripe", &in, st)) return st ? st->code : OZEC_EINVAL;
   if (nerased && (need(out, out_bytes, "output", &o, st) || need(out_crcs, crc_bytes, "checksum output", &oc, st)))
@@ -245,10 +250,16 @@ int ozm_reconstruct_host_batch(ozec_coder *dec, const ozm_buf *stripes, int64_t 
     if (need(expected, exp_bytes, "expected checksum", &ex, st) || need(mismatch, S * 4, "mismatch", &mm, st))
       return st ? st->code : OZEC_EINVAL;
   }
-  int rc = ozec_reconstruct_crc_host_batch(dec, in, stripe_stride, unit_stride, present, npresent, erased, nerased,
-                                           (uint8_t *)o, out_stride, cell_len, (size_t)S, (size_t)cell_len,
-                                           checksum_type, (size_t)bpc, (const uint32_t *)ex, 1, (uint32_t *)oc, 1,
-                                           (int32_t *)mm, 0);
+  int rc;
+  if (dl)
+    rc = ozec_reconstruct_digest_host_batch(dec, in, stripe_stride, unit_stride, present, npresent, erased, nerased,
+                                            (uint8_t *)o, out_stride, cell_len, (size_t)S, (size_t)cell_len,
+                                            checksum_type, (size_t)bpc, ex, (uint8_t *)oc, (int32_t *)mm, 0);
+  else
+    rc = ozec_reconstruct_crc_host_batch(dec, in, stripe_stride, unit_stride, present, npresent, erased, nerased,
+                                         (uint8_t *)o, out_stride, cell_len, (size_t)S, (size_t)cell_len,
+                                         checksum_type, (size_t)bpc, (const uint32_t *)ex, 1, (uint32_t *)oc, 1,
+                                         (int32_t *)mm, 0);
   return rc ? ozm_fail(rc, NULL, st) : ok(st);
 }
 

@@ -86,8 +86,10 @@ int ozm_digest_windows(int checksum_type, const ozm_buf *buf, int64_t len, int64
  * ozec_reconstruct_crc_host_batch).  stripes: [S][k+p][cell_len] at stripe_stride / unit_stride (absent and erased
  * units are never read); out: [S][nerased][cell_len]; out_crcs: [S][nerased][nwin] and expected: [S][k+p][nwin]
  * 4-byte big-endian values (Ints.toByteArray, Checksum.java:59-70); mismatch: [S] native-order ints, -1 or the first
- * failing unit * nwin + window.  expected (and mismatch) may be absent: no verification.  Every buffer's capacity is
- * checked against its layout before anything runs. */
+ * failing unit * nwin + window.  expected (and mismatch) may be absent: no verification.  For checksum_type SHA256 /
+ * MD5 (ozec_reconstruct_digest_host_batch) out_crcs is [S][nerased][nwin][digest length] and expected
+ * [S][k+p][nwin][digest length], the bytes of MessageDigest.digest().  Every buffer's capacity is checked against its
+ * layout, with that element size, before anything runs. */
 int ozm_reconstruct_host_batch(ozec_coder *dec, const ozm_buf *stripes, int64_t stripe_stride, int64_t unit_stride,
                                const int *present, int npresent, const int *erased, int nerased, const ozm_buf *out,
                                int64_t num_stripes, int64_t cell_len, int checksum_type, int64_t bytes_per_checksum,
@@ -96,7 +98,9 @@ int ozm_reconstruct_host_batch(ozec_coder *dec, const ozm_buf *stripes, int64_t 
 
 /* HipStripeQueue.submit (ozec_stripe_queue_submit): nd == k data cells and np == p parity cells of len bytes from
  * their offsets; crcs (absent = no CRCs wanted) must hold (k + coded rows) * ceil(len / bpc) 4-byte values from its
- * offset when the queue computes checksums.  *ticket identifies the stripe. */
+ * offset when the queue computes checksums; on a SHA256 / MD5 queue (ozec_stripe_queue_submit_digests) it must hold
+ * (k + coded rows) * ceil(len / bpc) digests of ozec_digest_length(type) bytes, [unit][window][digest length].
+ * *ticket identifies the stripe. */
 int ozm_queue_submit(ozec_stripe_queue *q, const ozm_buf *data, int nd, const ozm_buf *parity, int np, int64_t len,
                      const ozm_buf *crcs, uint64_t *ticket, ozm_status *st);
 

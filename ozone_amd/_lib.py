@@ -110,6 +110,18 @@ _SIGS = {
                                                   ctypes.c_int, c_voidp, c_i64, c_i64, c_size, c_size, ctypes.c_int,
                                                   c_size, c_voidp, ctypes.c_int, c_voidp, ctypes.c_int, c_voidp,
                                                   c_voidp]),
+    "ozec_encode_digest_batch": (ctypes.c_int, [c_voidp, c_voidp, c_i64, c_i64, c_voidp, c_i64, c_i64, c_size, c_size,
+                                                ctypes.c_int, c_size, c_voidp, c_voidp]),
+    "ozec_reconstruct_digest_batch": (ctypes.c_int, [c_voidp, c_voidp, c_i64, c_i64, c_intp, ctypes.c_int, c_intp,
+                                                     ctypes.c_int, c_voidp, c_i64, c_i64, c_size, c_size, ctypes.c_int,
+                                                     c_size, c_voidp, c_voidp, c_voidp, c_voidp]),
+    "ozec_encode_digest_host_batch": (ctypes.c_int, [c_voidp, c_voidp, c_i64, c_i64, c_voidp, c_i64, c_i64, c_size,
+                                                     c_size, ctypes.c_int, c_size, c_voidp, c_size]),
+    "ozec_reconstruct_digest_host_batch": (ctypes.c_int, [c_voidp, c_voidp, c_i64, c_i64, c_intp, ctypes.c_int, c_intp,
+                                                          ctypes.c_int, c_voidp, c_i64, c_i64, c_size, c_size,
+                                                          ctypes.c_int, c_size, c_voidp, c_voidp, c_voidp, c_size]),
+    "ozec_stripe_queue_submit_digests": (ctypes.c_int, [c_voidp, c_ptrs, c_ptrs, c_size, c_voidp,
+                                                        ctypes.POINTER(ctypes.c_uint64)]),
     "ozec_reconstruct_crc_host_batch": (ctypes.c_int, [c_voidp, c_voidp, c_i64, c_i64, c_intp, ctypes.c_int, c_intp,
                                                        ctypes.c_int, c_voidp, c_i64, c_i64, c_size, c_size, ctypes.c_int,
                                                        c_size, c_voidp, ctypes.c_int, c_voidp, ctypes.c_int, c_voidp,

@@ -1403,17 +1403,21 @@ int ozec_encode_crc_block_groups(ozec_coder *enc, uint8_t *d_base, int64_t group
 static int encode_crc_host_batch_dev(ozec_coder *enc, const uint8_t *h_in, int64_t in_stripe_stride,
                                      int64_t in_unit_stride, uint8_t *h_out, int64_t out_stripe_stride,
                                      int64_t out_unit_stride, size_t num_stripes, size_t len, int checksum_type,
-                                     size_t bpc, uint32_t *h_crcs, int big_endian, size_t stripes_per_chunk) {
+                                     size_t bpc, uint8_t *h_crcs, size_t esz, int big_endian,
+                                     size_t stripes_per_chunk) {
+  // h_crcs: one element of esz bytes per window -- a uint32 CRC, or a SHA256 / MD5 digest (the digest form, whose
+  // chunks go through ozec_encode_digest_batch)
+  const bool digest = esz != sizeof(uint32_t);  // the digest forms pass a checked type and its digest length
   if (int rc = check_open(enc, "encode")) return rc;
   if (enc->decoder) return fail(OZEC_EINVAL, "not an encoder");
   if (len == 0 || num_stripes == 0) return OZEC_OK;
   const bool with_crc = checksum_type != OZEC_CHECKSUM_NONE;
   if (!h_in || !h_out || (with_crc && !h_crcs)) return fail(OZEC_EINVAL, "Invalid buffer found, not allowing null");
-  if (with_crc) {
+  if (with_crc && !digest) {
     CrcType t;
     if (int rc = crc_type_of(checksum_type, &t)) return rc;
-    if (bpc == 0) return fail(OZEC_EINVAL, "bytesPerChecksum must be positive");
   }
+  if (with_crc && bpc == 0) return fail(OZEC_EINVAL, "bytesPerChecksum must be positive");
   DevCtx *ctx;
   if (int rc = get_ctx(&ctx)) return rc;
   E2E &P = ctx->e2e;
@@ -1431,8 +1435,8 @@ static int encode_crc_host_batch_dev(ozec_coder *enc, const uint8_t *h_in, int64
   const size_t dunit = ozec::g_tune.host_pitch16.load(std::memory_order_relaxed) ? round_up(len, 16) : len;
   const size_t dstripe = static_cast<size_t>(k + p) * dunit;
   const size_t dcrc_off = round_up(C * dstripe, kStageAlign);            // then crcs [C][units][nwin]
-  const size_t dbytes = dcrc_off + C * units * nwin * sizeof(uint32_t);
-  const size_t ncrc = units * nwin;                                      // CRCs per stripe
+  const size_t dbytes = dcrc_off + C * units * nwin * esz;
+  const size_t ncrc = units * nwin * esz;                                // checksum bytes per stripe
   // which caller buffers need staging (pageable); the C5 batch is registered, so normally none
   const size_t in_span = (num_stripes - 1) * static_cast<size_t>(in_stripe_stride) +
                          (k - 1) * static_cast<size_t>(in_unit_stride) + len;
@@ -1440,7 +1444,7 @@ static int encode_crc_host_batch_dev(ozec_coder *enc, const uint8_t *h_in, int64
                           (p - 1) * static_cast<size_t>(out_unit_stride) + len;
   const bool in_pinned = range_pinned(h_in, in_span);
   const bool out_pinned = range_pinned(h_out, out_span);
-  const bool crc_pinned = !with_crc || range_pinned(h_crcs, num_stripes * ncrc * sizeof(uint32_t));
+  const bool crc_pinned = !with_crc || range_pinned(h_crcs, num_stripes * ncrc);
   const bool staged = !in_pinned || !out_pinned || !crc_pinned;
   if (!P.h2d) {
     OZEC_HIP(ozec::make_stream(&P.h2d));
@@ -1494,7 +1498,7 @@ static int encode_crc_host_batch_dev(ozec_coder *enc, const uint8_t *h_in, int64
           tasks.push_back({h_out + (s0 + i) * out_stripe_stride + r * out_unit_stride,
                            P.hstage[b] + i * dstripe + static_cast<size_t>(k + r) * dunit, len});
     if (with_crc && !crc_pinned)
-      tasks.push_back({h_crcs + s0 * ncrc, P.hstage[b] + dcrc_off, cs * ncrc * sizeof(uint32_t)});
+      tasks.push_back({h_crcs + s0 * ncrc, P.hstage[b] + dcrc_off, cs * ncrc});
     ozec::parallel_copy(tasks, ozec::CopyDir::kFromStaging, true, ctx->numa);
     return OZEC_OK;
   };
@@ -1552,10 +1556,14 @@ static int encode_crc_host_batch_dev(ozec_coder *enc, const uint8_t *h_in, int64
     OZEC_HIP(hipEventRecord(P.h2d_done[b], P.h2d));
     OZEC_HIP(hipStreamWaitEvent(P.comp, P.h2d_done[b], 0));
     const int64_t ds = static_cast<int64_t>(dstripe), us = static_cast<int64_t>(dunit);
-    uint32_t *dcrc = reinterpret_cast<uint32_t *>(d + dcrc_off);
-    if (with_crc) {
+    uint8_t *dcrc = d + dcrc_off;
+    if (digest) {
+      if (int rc = ozec_encode_digest_batch(enc, d, ds, us, d + static_cast<size_t>(k) * dunit, ds, us, cs, len,
+                                            checksum_type, bpc, dcrc, P.comp))
+        return rc;
+    } else if (with_crc) {
       if (int rc = ozec_encode_crc_batch(enc, d, ds, us, d + static_cast<size_t>(k) * dunit, ds, us, cs, len,
-                                         checksum_type, bpc, dcrc, big_endian, P.comp))
+                                         checksum_type, bpc, reinterpret_cast<uint32_t *>(dcrc), big_endian, P.comp))
         return rc;
     } else {
       if (int rc = ozec_encode_batch(enc, d, ds, us, d + static_cast<size_t>(k) * dunit, ds, us, cs, len, P.comp))
@@ -1586,8 +1594,8 @@ static int encode_crc_host_batch_dev(ozec_coder *enc, const uint8_t *h_in, int64
       }
     }
     if (with_crc)
-      OZEC_HIP(hipMemcpyAsync(crc_pinned ? reinterpret_cast<uint8_t *>(h_crcs + s0 * ncrc) : hs + dcrc_off, dcrc,
-                              cs * ncrc * sizeof(uint32_t), hipMemcpyDeviceToHost, P.d2h));
+      OZEC_HIP(hipMemcpyAsync(crc_pinned ? h_crcs + s0 * ncrc : hs + dcrc_off, dcrc, cs * ncrc, hipMemcpyDeviceToHost,
+                              P.d2h));
     OZEC_HIP(hipEventRecord(P.d2h_done[b], P.d2h));
   }
   if (staged) {
@@ -1729,6 +1737,169 @@ int ozec_digest_windows(int checksum_type, const uint8_t *data, size_t len, size
       });
 }
 
+// ---- stripes with SHA256 / MD5 window digests: the coding launch, then ONE digest launch over every unit of every
+//      stripe (digest.hpp DigestStripeArgs).  A digest launch costs at least one lane's walk over one window whatever
+//      the batch, so a call's launch count decides the time of a small batch. ---------------------------
+
+namespace {
+
+// the digest type of a stripe entry point; `twin` names the CRC-typed call a CRC / NONE type belongs to
+int stripe_digest_algo_of(int checksum_type, size_t bpc, const char *twin, int *algo) {
+  if (checksum_type == OZEC_CHECKSUM_SHA256) *algo = ozec::digest::kSha256;
+  else if (checksum_type == OZEC_CHECKSUM_MD5) *algo = ozec::digest::kMd5;
+  else return fail(OZEC_EINVAL, "unsupported digest type " + std::to_string(checksum_type) +
+                                    " (SHA256=4 and MD5=5; the CRC types and NONE go through " + twin + ")");
+  if (bpc == 0) return fail(OZEC_EINVAL, "bytesPerChecksum must be positive");
+  return OZEC_OK;
+}
+
+void stripe_digest_shape(ozec::DigestStripeArgs *g, size_t num_stripes, size_t len, size_t bpc) {
+  g->nstripes = static_cast<int64_t>(num_stripes);
+  g->len = static_cast<int64_t>(len);
+  g->bpc = static_cast<int64_t>(bpc);
+  g->nwin = static_cast<int64_t>((len + bpc - 1) / bpc);
+}
+
+}  // namespace
+
+int ozec_encode_digest_batch(ozec_coder *enc, const uint8_t *d_in, int64_t in_stripe_stride, int64_t in_unit_stride,
+                             uint8_t *d_out, int64_t out_stripe_stride, int64_t out_unit_stride, size_t num_stripes,
+                             size_t len, int checksum_type, size_t bpc, uint8_t *d_digests, void *stream) {
+  ozec::StatScope stat_(OZEC_OP_FUSED, enc ? static_cast<uint64_t>(enc->k) * len * num_stripes : 0);
+  // the type first: a caller without a device has no coder to show, and still learns which call it wants
+  int algo;
+  if (int rc = stripe_digest_algo_of(checksum_type, bpc, "ozec_encode_crc_batch", &algo)) return rc;
+  if (int rc = check_open(enc, "encode")) return rc;
+  if (enc->decoder) return fail(OZEC_EINVAL, "not an encoder");
+  if (len == 0 || num_stripes == 0) return OZEC_OK;
+  if (!d_in || !d_out || !d_digests) return fail(OZEC_EINVAL, "Invalid buffer found, not allowing null");
+  if ((len + bpc - 1) / bpc > static_cast<size_t>(INT32_MAX)) return fail(OZEC_EINVAL, "more than 2^31 - 1 windows per cell");
+  const int k = enc->k, rows = out_rows(enc);
+  if (int rc = check_limits(k, rows)) return rc;
+  DevCtx *ctx;
+  if (int rc = get_ctx(&ctx)) return rc;
+  hipStream_t st = pick_stream(ctx, stream);
+  CodeArgs a{};
+  a.in = d_in;
+  a.out = d_out;
+  a.in_stripe_stride = in_stripe_stride;
+  a.out_stripe_stride = out_stripe_stride;
+  a.nstripes = static_cast<int64_t>(num_stripes);
+  a.len = static_cast<int64_t>(len);
+  std::vector<uint8_t> coef;
+  encode_rows(enc, coef);
+  fill_coef(a, rows, k, coef.data());
+  for (int j = 0; j < k; ++j) a.in_off[j] = j * in_unit_stride;
+  for (int r = 0; r < rows; ++r) a.out_off[r] = r * out_unit_stride;
+  OZEC_HIP(ozec::launch_code(a, st));
+  ozec::DigestStripeArgs g{};
+  stripe_digest_shape(&g, num_stripes, len, bpc);
+  g.buf[0] = d_in;
+  g.buf[1] = d_out;
+  g.stripe_stride[0] = in_stripe_stride;
+  g.stripe_stride[1] = out_stripe_stride;
+  g.nunits = g.out_units = k + rows;
+  g.out = d_digests;
+  for (int u = 0; u < k + rows; ++u) {
+    ozec::DigestUnit &n = g.unit[u];
+    n.buf = u < k ? 0 : 1;
+    n.off = u < k ? u * in_unit_stride : (u - k) * out_unit_stride;
+    n.slot = static_cast<uint16_t>(u);
+  }
+  OZEC_HIP(ozec::launch_digest_stripes(algo, g, st));
+  // XOR with p > 1: every output is reset, only outputs[0] is coded, as in ozec_encode_batch
+  for (int r = rows; r < enc->p; ++r)
+    OZEC_HIP(hipMemset2DAsync(d_out + r * out_unit_stride, out_stripe_stride, 0, len, num_stripes, st));
+  return OZEC_OK;
+}
+
+int ozec_reconstruct_digest_batch(ozec_coder *dec, const uint8_t *d_in, int64_t in_stripe_stride, int64_t in_unit_stride,
+                                  const int *present_units, int num_present, const int *erased, int n_erased,
+                                  uint8_t *d_out, int64_t out_stripe_stride, int64_t out_unit_stride, size_t num_stripes,
+                                  size_t len, int checksum_type, size_t bpc, const uint8_t *d_expected,
+                                  uint8_t *d_out_digests, int32_t *d_mismatch, void *stream) {
+  ozec::StatScope stat_(OZEC_OP_FUSED, dec ? static_cast<uint64_t>(dec->k) * len * num_stripes : 0);
+  // the type first: a caller without a device has no coder to show, and still learns which call it wants
+  int algo;
+  if (int rc = stripe_digest_algo_of(checksum_type, bpc, "ozec_reconstruct_crc_batch", &algo)) return rc;
+  if (int rc = check_open(dec, "decode")) return rc;
+  if (!dec->decoder) return fail(OZEC_EINVAL, "not a decoder");
+  const int n_all = dec->k + dec->p;
+  if (num_present < 0 || (num_present > 0 && !present_units)) return fail(OZEC_EINVAL, "invalid present units");
+  bool present[256] = {false};
+  for (int i = 0; i < num_present; ++i) {
+    if (present_units[i] < 0 || present_units[i] >= n_all) return fail(OZEC_EINVAL, "present unit out of range");
+    present[present_units[i]] = true;
+  }
+  std::vector<int> units;
+  std::vector<uint8_t> rows;
+  if (int rc = plan_decode(dec, present, erased, n_erased, units, rows)) return rc;
+  if (num_stripes == 0) return OZEC_OK;
+  if (!d_in || (n_erased && (!d_out || !d_out_digests)))
+    return fail(OZEC_EINVAL, "Invalid buffer found, not allowing null");
+  if (d_expected && !d_mismatch) return fail(OZEC_EINVAL, "verification needs a mismatch buffer");
+  const size_t nwin = (len + bpc - 1) / bpc;
+  if (nwin * static_cast<size_t>(n_all) > static_cast<size_t>(INT32_MAX))
+    return fail(OZEC_EINVAL, "(k + p) * windows does not fit the int32 mismatch report");
+  const int nin = static_cast<int>(units.size());
+  const int nrows = dec->codec == OZEC_CODEC_XOR ? (n_erased ? 1 : 0) : n_erased;
+  if (nrows)
+    if (int rc = check_limits(nin, nrows)) return rc;
+  if (nin + n_erased > ozec::kDigestMaxUnits) return fail(OZEC_EUNSUPPORTED, "too many units for one digest launch");
+  DevCtx *ctx;
+  if (int rc = get_ctx(&ctx)) return rc;
+  hipStream_t st = pick_stream(ctx, stream);
+  if (d_mismatch)
+    OZEC_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_mismatch), 0x7fffffff, num_stripes, st));
+  if (len > 0) {
+    if (nrows) {
+      CodeArgs a{};
+      a.in = d_in;
+      a.out = d_out;
+      a.in_stripe_stride = in_stripe_stride;
+      a.out_stripe_stride = out_stripe_stride;
+      a.nstripes = static_cast<int64_t>(num_stripes);
+      a.len = static_cast<int64_t>(len);
+      fill_coef(a, nrows, nin, rows.data());
+      for (int j = 0; j < nin; ++j) a.in_off[j] = units[j] * in_unit_stride;
+      for (int r = 0; r < nrows; ++r) a.out_off[r] = r * out_unit_stride;
+      OZEC_HIP(ozec::launch_code(a, st));
+    }
+    for (int r = nrows; r < n_erased; ++r)  // XOR decoders zero-fill outputs beyond erasedIndexes[0]
+      OZEC_HIP(hipMemset2DAsync(d_out + r * out_unit_stride, out_stripe_stride, 0, len, num_stripes, st));
+    // one digest launch: the read units' lanes verify (only when stored digests were given), the rebuilt units' compute
+    ozec::DigestStripeArgs g{};
+    stripe_digest_shape(&g, num_stripes, len, bpc);
+    g.buf[0] = d_in;
+    g.buf[1] = d_out;
+    g.stripe_stride[0] = in_stripe_stride;
+    g.stripe_stride[1] = out_stripe_stride;
+    g.out_units = n_erased;
+    g.exp_units = n_all;
+    g.out = d_out_digests;
+    g.expected = d_expected;
+    g.mismatch = d_mismatch;
+    int nu = 0;
+    for (int j = 0; j < nin && d_expected; ++j) {
+      ozec::DigestUnit &n = g.unit[nu++];
+      n.buf = 0;
+      n.verify = 1;
+      n.off = units[j] * in_unit_stride;
+      n.slot = static_cast<uint16_t>(units[j]);
+    }
+    for (int r = 0; r < n_erased; ++r) {
+      ozec::DigestUnit &n = g.unit[nu++];
+      n.buf = 1;
+      n.off = r * out_unit_stride;
+      n.slot = static_cast<uint16_t>(r);
+    }
+    g.nunits = nu;
+    OZEC_HIP(ozec::launch_digest_stripes(algo, g, st));
+  }
+  if (d_mismatch) OZEC_HIP(ozec::launch_finish_mismatch(d_mismatch, static_cast<int64_t>(num_stripes), st));
+  return OZEC_OK;
+}
+
 int ozec_reconstruct_crc_batch(ozec_coder *dec, const uint8_t *d_in, int64_t in_stripe_stride, int64_t in_unit_stride,
                                const int *present_units, int num_present, const int *erased, int n_erased,
                                uint8_t *d_out, int64_t out_stripe_stride, int64_t out_unit_stride, size_t num_stripes,
@@ -1847,9 +2018,12 @@ static int reconstruct_crc_host_batch_dev(ozec_coder *dec, const uint8_t *h_in, 
                                           int64_t in_unit_stride, const int *present_units, int num_present,
                                           const int *erased, int n_erased, uint8_t *h_out, int64_t out_stripe_stride,
                                           int64_t out_unit_stride, size_t num_stripes, size_t len, int checksum_type,
-                                          size_t bpc, const uint32_t *h_expected, int expected_big_endian,
-                                          uint32_t *h_out_crcs, int out_big_endian, int32_t *h_mismatch,
+                                          size_t bpc, const uint8_t *h_expected, int expected_big_endian,
+                                          uint8_t *h_out_crcs, size_t esz, int out_big_endian, int32_t *h_mismatch,
                                           size_t stripes_per_chunk) {
+  // h_expected / h_out_crcs: one element of esz bytes per window -- a uint32 CRC, or a SHA256 / MD5 digest (the digest
+  // form, whose chunks go through ozec_reconstruct_digest_batch)
+  const bool digest = esz != sizeof(uint32_t);  // the digest forms pass a checked type and its digest length
   if (int rc = check_open(dec, "decode")) return rc;
   if (!dec->decoder) return fail(OZEC_EINVAL, "not a decoder");
   const int n_all = dec->k + dec->p;
@@ -1862,11 +2036,11 @@ static int reconstruct_crc_host_batch_dev(ozec_coder *dec, const uint8_t *h_in, 
   std::vector<int> units;
   std::vector<uint8_t> rows;
   if (int rc = plan_decode(dec, present, erased, n_erased, units, rows)) return rc;
-  {
+  if (!digest) {
     CrcType t;
     if (int rc = crc_type_of(checksum_type, &t)) return rc;
-    if (bpc == 0) return fail(OZEC_EINVAL, "bytesPerChecksum must be positive");
   }
+  if (bpc == 0) return fail(OZEC_EINVAL, "bytesPerChecksum must be positive");
   if (num_stripes == 0 || len == 0) {
     if (h_mismatch)
       for (size_t s = 0; s < num_stripes; ++s) h_mismatch[s] = -1;
@@ -1889,9 +2063,9 @@ static int reconstruct_crc_host_batch_dev(ozec_coder *dec, const uint8_t *h_in, 
   const size_t dstripe = static_cast<size_t>(n_all) * dunit, ostripe = static_cast<size_t>(e) * dunit;
   const size_t dout_off = round_up(C * dstripe, kStageAlign);
   const size_t dexp_off = round_up(dout_off + C * ostripe, kStageAlign);
-  const size_t dexp_bytes = h_expected ? C * n_all * nwin * sizeof(uint32_t) : 0;
+  const size_t dexp_bytes = h_expected ? C * n_all * nwin * esz : 0;
   const size_t docrc_off = round_up(dexp_off + dexp_bytes, kStageAlign);
-  const size_t dmis_off = round_up(docrc_off + C * e * nwin * sizeof(uint32_t), kStageAlign);
+  const size_t dmis_off = round_up(docrc_off + C * e * nwin * esz, kStageAlign);
   const size_t dbytes = dmis_off + C * sizeof(int32_t);
   // runs of consecutive unit indexes among the units read: one rectangular copy per run and chunk
   std::vector<std::pair<int, int>> runs;
@@ -1907,8 +2081,8 @@ static int reconstruct_crc_host_batch_dev(ozec_coder *dec, const uint8_t *h_in, 
                             : 0;
   const bool in_pinned = range_pinned(h_in, in_span);
   const bool out_pinned = !e || range_pinned(h_out, out_span);
-  const bool exp_pinned = !h_expected || range_pinned(h_expected, num_stripes * n_all * nwin * sizeof(uint32_t));
-  const bool ocrc_pinned = !e || range_pinned(h_out_crcs, num_stripes * e * nwin * sizeof(uint32_t));
+  const bool exp_pinned = !h_expected || range_pinned(h_expected, num_stripes * n_all * nwin * esz);
+  const bool ocrc_pinned = !e || range_pinned(h_out_crcs, num_stripes * e * nwin * esz);
   const bool mis_pinned = !h_expected || range_pinned(h_mismatch, num_stripes * sizeof(int32_t));
   const bool staged = !in_pinned || !out_pinned || !exp_pinned || !ocrc_pinned || !mis_pinned;
   if (!P.h2d) {
@@ -1961,7 +2135,7 @@ static int reconstruct_crc_host_batch_dev(ozec_coder *dec, const uint8_t *h_in, 
           tasks.push_back({h_out + (s0 + i) * out_stripe_stride + r * out_unit_stride,
                            P.hstage[b] + dout_off + i * ostripe + static_cast<size_t>(r) * dunit, len});
     if (!ocrc_pinned)
-      tasks.push_back({h_out_crcs + s0 * e * nwin, P.hstage[b] + docrc_off, cs * e * nwin * sizeof(uint32_t)});
+      tasks.push_back({h_out_crcs + s0 * e * nwin * esz, P.hstage[b] + docrc_off, cs * e * nwin * esz});
     if (!mis_pinned) tasks.push_back({h_mismatch + s0, P.hstage[b] + dmis_off, cs * sizeof(int32_t)});
     ozec::parallel_copy(tasks, ozec::CopyDir::kFromStaging, true, ctx->numa);
     return OZEC_OK;
@@ -1981,7 +2155,7 @@ static int reconstruct_crc_host_batch_dev(ozec_coder *dec, const uint8_t *h_in, 
             tasks.push_back({hs + i * dstripe + static_cast<size_t>(u) * dunit,
                              h_in + (s0 + i) * in_stripe_stride + u * in_unit_stride, len});
       if (!exp_pinned)
-        tasks.push_back({hs + dexp_off, h_expected + s0 * n_all * nwin, cs * n_all * nwin * sizeof(uint32_t)});
+        tasks.push_back({hs + dexp_off, h_expected + s0 * n_all * nwin * esz, cs * n_all * nwin * esz});
       ozec::parallel_copy(tasks, ozec::CopyDir::kToStaging, true, ctx->numa);
     }
     if (c >= static_cast<size_t>(E2E::NB)) {
@@ -2009,18 +2183,25 @@ static int reconstruct_crc_host_batch_dev(ozec_coder *dec, const uint8_t *h_in, 
       }
     }
     if (h_expected)
-      OZEC_HIP(hipMemcpyAsync(d + dexp_off, exp_pinned ? reinterpret_cast<const uint8_t *>(h_expected + s0 * n_all * nwin)
-                                                       : hs + dexp_off,
-                              cs * n_all * nwin * sizeof(uint32_t), hipMemcpyHostToDevice, P.h2d));
+      OZEC_HIP(hipMemcpyAsync(d + dexp_off, exp_pinned ? h_expected + s0 * n_all * nwin * esz : hs + dexp_off,
+                              cs * n_all * nwin * esz, hipMemcpyHostToDevice, P.h2d));
     OZEC_HIP(hipEventRecord(P.h2d_done[b], P.h2d));
     OZEC_HIP(hipStreamWaitEvent(P.comp, P.h2d_done[b], 0));
-    if (int rc = ozec_reconstruct_crc_batch(
-            dec, d, static_cast<int64_t>(dstripe), static_cast<int64_t>(dunit), present_units, num_present, erased, e,
-            d + dout_off, static_cast<int64_t>(ostripe), static_cast<int64_t>(dunit), cs, len, checksum_type, bpc,
-            h_expected ? reinterpret_cast<const uint32_t *>(d + dexp_off) : nullptr, expected_big_endian,
-            reinterpret_cast<uint32_t *>(d + docrc_off), out_big_endian,
-            h_expected ? reinterpret_cast<int32_t *>(d + dmis_off) : nullptr, P.comp))
+    if (digest) {
+      if (int rc = ozec_reconstruct_digest_batch(
+              dec, d, static_cast<int64_t>(dstripe), static_cast<int64_t>(dunit), present_units, num_present, erased, e,
+              d + dout_off, static_cast<int64_t>(ostripe), static_cast<int64_t>(dunit), cs, len, checksum_type, bpc,
+              h_expected ? d + dexp_off : nullptr, d + docrc_off,
+              h_expected ? reinterpret_cast<int32_t *>(d + dmis_off) : nullptr, P.comp))
+        return rc;
+    } else if (int rc = ozec_reconstruct_crc_batch(
+                   dec, d, static_cast<int64_t>(dstripe), static_cast<int64_t>(dunit), present_units, num_present, erased,
+                   e, d + dout_off, static_cast<int64_t>(ostripe), static_cast<int64_t>(dunit), cs, len, checksum_type,
+                   bpc, h_expected ? reinterpret_cast<const uint32_t *>(d + dexp_off) : nullptr, expected_big_endian,
+                   reinterpret_cast<uint32_t *>(d + docrc_off), out_big_endian,
+                   h_expected ? reinterpret_cast<int32_t *>(d + dmis_off) : nullptr, P.comp)) {
       return rc;
+    }
     OZEC_HIP(hipEventRecord(P.comp_done[b], P.comp));
     OZEC_HIP(hipStreamWaitEvent(P.d2h, P.comp_done[b], 0));
     if (e) {
@@ -2040,8 +2221,8 @@ static int reconstruct_crc_host_batch_dev(ozec_coder *dec, const uint8_t *h_in, 
                                     d + dout_off + i * ostripe + static_cast<size_t>(r) * len, len, hipMemcpyDeviceToHost,
                                     P.d2h));
       }
-      OZEC_HIP(hipMemcpyAsync(ocrc_pinned ? reinterpret_cast<uint8_t *>(h_out_crcs + s0 * e * nwin) : hs + docrc_off,
-                              d + docrc_off, cs * e * nwin * sizeof(uint32_t), hipMemcpyDeviceToHost, P.d2h));
+      OZEC_HIP(hipMemcpyAsync(ocrc_pinned ? h_out_crcs + s0 * e * nwin * esz : hs + docrc_off, d + docrc_off,
+                              cs * e * nwin * esz, hipMemcpyDeviceToHost, P.d2h));
     }
     if (h_expected)
       OZEC_HIP(hipMemcpyAsync(mis_pinned ? reinterpret_cast<uint8_t *>(h_mismatch + s0) : hs + dmis_off, d + dmis_off,
@@ -2140,8 +2321,68 @@ int ozec_encode_crc_host_batch(ozec_coder *enc, const uint8_t *h_in, int64_t in_
   return host_batch_split(enc, num_stripes, e2e_chunk_of(stripes_per_chunk), [&](size_t s0, size_t s1) {
     return encode_crc_host_batch_dev(enc, h_in + s0 * in_stripe_stride, in_stripe_stride, in_unit_stride,
                                      h_out + s0 * out_stripe_stride, out_stripe_stride, out_unit_stride, s1 - s0, len,
-                                     checksum_type, bpc, with_crc ? h_crcs + s0 * ncrc : nullptr, big_endian,
-                                     stripes_per_chunk);
+                                     checksum_type, bpc, with_crc ? reinterpret_cast<uint8_t *>(h_crcs + s0 * ncrc) : nullptr,
+                                     sizeof(uint32_t), big_endian, stripes_per_chunk);
+  });
+}
+
+// The digest forms of the two host batches.  Which window sizes keep them link-bound: a chunk is one coding launch and
+// one digest launch, and the digest launch lasts at least one lane's serial walk over one window (0.65 ms
+// for SHA-256 at 16 KiB), against about 3.6 ms of H2D for a 32-stripe rs-6-3 chunk of 1 MiB cells -- so windows up to
+// some tens of KiB hide behind the link, while at 1 MiB windows a chunk is a few hundred lanes and the call is bound
+// by their serial hashing (single GB/s for SHA-256).  More stripes per chunk do not help there; smaller windows do.
+int ozec_encode_digest_host_batch(ozec_coder *enc, const uint8_t *h_in, int64_t in_stripe_stride,
+                                  int64_t in_unit_stride, uint8_t *h_out, int64_t out_stripe_stride,
+                                  int64_t out_unit_stride, size_t num_stripes, size_t len, int checksum_type, size_t bpc,
+                                  uint8_t *h_digests, size_t stripes_per_chunk) {
+  ozec::StatScope stat_(OZEC_OP_HOST_BATCH, enc ? static_cast<uint64_t>(enc->k) * len * num_stripes : 0);
+  // the type first: a caller without a device has no coder to show, and still learns which call it wants
+  int algo;
+  if (int rc = stripe_digest_algo_of(checksum_type, bpc, "ozec_encode_crc_host_batch", &algo)) return rc;
+  if (int rc = check_open(enc, "encode")) return rc;
+  if (enc->decoder) return fail(OZEC_EINVAL, "not an encoder");
+  if (len == 0 || num_stripes == 0) return OZEC_OK;
+  if (!h_in || !h_out || !h_digests) return fail(OZEC_EINVAL, "Invalid buffer found, not allowing null");
+  if ((len + bpc - 1) / bpc > static_cast<size_t>(INT32_MAX)) return fail(OZEC_EINVAL, "more than 2^31 - 1 windows per cell");
+  const size_t dl = ozec_digest_length(checksum_type);
+  const size_t nd = static_cast<size_t>(enc->k + out_rows(enc)) * ((len + bpc - 1) / bpc) * dl;
+  return host_batch_split(enc, num_stripes, e2e_chunk_of(stripes_per_chunk), [&](size_t s0, size_t s1) {
+    return encode_crc_host_batch_dev(enc, h_in + s0 * in_stripe_stride, in_stripe_stride, in_unit_stride,
+                                     h_out + s0 * out_stripe_stride, out_stripe_stride, out_unit_stride, s1 - s0, len,
+                                     checksum_type, bpc, h_digests + s0 * nd, dl, 0, stripes_per_chunk);
+  });
+}
+
+int ozec_reconstruct_digest_host_batch(ozec_coder *dec, const uint8_t *h_in, int64_t in_stripe_stride,
+                                       int64_t in_unit_stride, const int *present_units, int num_present,
+                                       const int *erased, int n_erased, uint8_t *h_out, int64_t out_stripe_stride,
+                                       int64_t out_unit_stride, size_t num_stripes, size_t len, int checksum_type,
+                                       size_t bpc, const uint8_t *h_expected, uint8_t *h_out_digests, int32_t *h_mismatch,
+                                       size_t stripes_per_chunk) {
+  ozec::StatScope stat_(OZEC_OP_HOST_BATCH, dec ? static_cast<uint64_t>(dec->k) * len * num_stripes : 0);
+  // the type first: a caller without a device has no coder to show, and still learns which call it wants
+  int algo;
+  if (int rc = stripe_digest_algo_of(checksum_type, bpc, "ozec_reconstruct_crc_host_batch", &algo)) return rc;
+  if (int rc = check_open(dec, "decode")) return rc;
+  if (!dec->decoder) return fail(OZEC_EINVAL, "not a decoder");
+  const size_t dl = ozec_digest_length(checksum_type);
+  const size_t nwin = (len + bpc - 1) / bpc, n_all = static_cast<size_t>(dec->k + dec->p);
+  if (nwin * n_all > static_cast<size_t>(INT32_MAX))
+    return fail(OZEC_EINVAL, "(k + p) * windows does not fit the int32 mismatch report");
+  // the other argument errors (in the single-device path's order) and empty batches: no split
+  if (num_stripes == 0 || len == 0 || n_erased < 0 || !h_in || (n_erased && (!h_out || !h_out_digests)) ||
+      (h_expected && !h_mismatch))
+    return reconstruct_crc_host_batch_dev(dec, h_in, in_stripe_stride, in_unit_stride, present_units, num_present,
+                                          erased, n_erased, h_out, out_stripe_stride, out_unit_stride, num_stripes, len,
+                                          checksum_type, bpc, h_expected, 0, h_out_digests, dl, 0, h_mismatch,
+                                          stripes_per_chunk);
+  return host_batch_split(dec, num_stripes, e2e_chunk_of(stripes_per_chunk), [&](size_t s0, size_t s1) {
+    return reconstruct_crc_host_batch_dev(
+        dec, h_in + s0 * in_stripe_stride, in_stripe_stride, in_unit_stride, present_units, num_present, erased,
+        n_erased, h_out ? h_out + s0 * out_stripe_stride : nullptr, out_stripe_stride, out_unit_stride, s1 - s0, len,
+        checksum_type, bpc, h_expected ? h_expected + s0 * n_all * nwin * dl : nullptr, 0,
+        h_out_digests ? h_out_digests + s0 * static_cast<size_t>(n_erased) * nwin * dl : nullptr, dl, 0,
+        h_mismatch ? h_mismatch + s0 : nullptr, stripes_per_chunk);
   });
 }
 
@@ -2159,16 +2400,18 @@ int ozec_reconstruct_crc_host_batch(ozec_coder *dec, const uint8_t *h_in, int64_
       (h_expected && !h_mismatch))
     return reconstruct_crc_host_batch_dev(dec, h_in, in_stripe_stride, in_unit_stride, present_units, num_present,
                                           erased, n_erased, h_out, out_stripe_stride, out_unit_stride, num_stripes, len,
-                                          checksum_type, bpc, h_expected, expected_big_endian, h_out_crcs,
+                                          checksum_type, bpc, reinterpret_cast<const uint8_t *>(h_expected),
+                                          expected_big_endian, reinterpret_cast<uint8_t *>(h_out_crcs), sizeof(uint32_t),
                                           out_big_endian, h_mismatch, stripes_per_chunk);
   const size_t nwin = (len + bpc - 1) / bpc, n_all = static_cast<size_t>(dec->k + dec->p);
   return host_batch_split(dec, num_stripes, e2e_chunk_of(stripes_per_chunk), [&](size_t s0, size_t s1) {
     return reconstruct_crc_host_batch_dev(
         dec, h_in + s0 * in_stripe_stride, in_stripe_stride, in_unit_stride, present_units, num_present, erased,
         n_erased, h_out ? h_out + s0 * out_stripe_stride : nullptr, out_stripe_stride, out_unit_stride, s1 - s0, len,
-        checksum_type, bpc, h_expected ? h_expected + s0 * n_all * nwin : nullptr, expected_big_endian,
-        h_out_crcs ? h_out_crcs + s0 * static_cast<size_t>(n_erased) * nwin : nullptr, out_big_endian,
-        h_mismatch ? h_mismatch + s0 : nullptr, stripes_per_chunk);
+        checksum_type, bpc, h_expected ? reinterpret_cast<const uint8_t *>(h_expected + s0 * n_all * nwin) : nullptr,
+        expected_big_endian,
+        h_out_crcs ? reinterpret_cast<uint8_t *>(h_out_crcs + s0 * static_cast<size_t>(n_erased) * nwin) : nullptr,
+        sizeof(uint32_t), out_big_endian, h_mismatch ? h_mismatch + s0 : nullptr, stripes_per_chunk);
   });
 }
 

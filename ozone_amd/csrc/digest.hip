@@ -10,6 +10,10 @@
 // the wave fetches 256-byte segments of its 64 windows with coalesced loads and hands them to the lanes through LDS.
 // Whole blocks lie inside the window; the 0-63 tail bytes are read with 4-byte loads that end at or before the window's
 // end and at most three single-byte loads, so nothing outside [cell, cell + len) is touched.
+//
+// Stripes (digest_stripes, digest_stripes_coop; DigestStripeArgs): the same two forms over the units of coded stripes,
+// which lie in two buffers and are computed or verified unit by unit, all in one launch -- a digest launch lasts at
+// least one lane's walk over one window, so the stripe paths make one per batch.
 #include "device.hpp"
 #include "digest.hpp"
 #include "digest_core.hpp"
@@ -34,13 +38,11 @@ __device__ __forceinline__ void load_tail(const uint8_t *p, uint32_t r, uint32_t
   }
 }
 
-// Blocks [i0, nb) of the window at `win` (N bytes, nb whole blocks) into the state, then the padding and the result of
-// unit u = (c, w): the digest stored, or compared with the expected one.
-template <int A, bool VERIFY>
-__device__ __forceinline__ void digest_rest(const DigestArgs &a, uint32_t *st, const uint8_t *win, int64_t i0, int64_t nb,
-                                            int64_t N, int64_t u, int64_t c, int64_t w) {
-  constexpr int SW = dg::Traits<A>::kStateWords;
-  constexpr int DL = dg::Traits<A>::kDigestLen;
+// Blocks [i0, nb) of the window at `win` (N bytes, nb whole blocks) into the state, then the padding: o = the digest's
+// words in memory order.  Shared by the cell kernels (digest_rest) and the stripe kernels (digest_stripes*).
+template <int A>
+__device__ __forceinline__ void digest_blocks(uint32_t *st, const uint8_t *win, int64_t i0, int64_t nb, int64_t N,
+                                              uint32_t (&o)[dg::Traits<A>::kStateWords]) {
   // Two register sets: the loads of the next block are issued before the compress of the current one and land in the
   // other set, so no copy sits between a load and its use.  Three things keep hipcc from undoing that (read from the
   // ISA): the loads are unconditional -- past the last whole block the cursor stays on it and the surplus load
@@ -71,23 +73,42 @@ __device__ __forceinline__ void digest_rest(const DigestArgs &a, uint32_t *st, c
     for (int j = 0; j < 16; ++j) m[j] = k == 0 ? xa[j] : k == 1 ? b0[j] : b1[j];
     dg::compress<A>(st, m);
   }
-  uint32_t o[SW];
   dg::digest_words<A>(st, o);
+}
+
+// o differs from the stored digest at e
+template <int A>
+__device__ __forceinline__ bool digest_differs(const uint32_t (&o)[dg::Traits<A>::kStateWords], const uint8_t *e) {
+  constexpr int SW = dg::Traits<A>::kStateWords;
+  uint32_t x[SW];
+  __builtin_memcpy(x, e, dg::Traits<A>::kDigestLen);
+  uint32_t diff = 0;
+#pragma unroll
+  for (int j = 0; j < SW; ++j) diff |= x[j] ^ o[j];
+  return diff != 0;
+}
+
+template <int A>
+__device__ __forceinline__ void digest_store(const uint32_t (&o)[dg::Traits<A>::kStateWords], uint8_t *dst) {
+#pragma unroll
+  for (int j = 0; j < dg::Traits<A>::kStateWords; j += 4) {
+    const uint4 v = make_uint4(o[j], o[j + 1], o[j + 2], o[j + 3]);
+    __builtin_memcpy(dst + 4 * j, &v, 16);
+    store_data_hold(v);
+  }
+}
+
+// digest_blocks, then the result of unit u = (c, w): the digest stored, or compared with the expected one
+template <int A, bool VERIFY>
+__device__ __forceinline__ void digest_rest(const DigestArgs &a, uint32_t *st, const uint8_t *win, int64_t i0, int64_t nb,
+                                            int64_t N, int64_t u, int64_t c, int64_t w) {
+  constexpr int DL = dg::Traits<A>::kDigestLen;
+  uint32_t o[dg::Traits<A>::kStateWords];
+  digest_blocks<A>(st, win, i0, nb, N, o);
   if constexpr (VERIFY) {
-    uint32_t e[SW];
-    __builtin_memcpy(e, a.expected + u * DL, DL);
-    uint32_t diff = 0;
-#pragma unroll
-    for (int j = 0; j < SW; ++j) diff |= e[j] ^ o[j];
-    if (diff != 0) atomicMin(a.mismatch + c, static_cast<int32_t>(w));
+    if (digest_differs<A>(o, a.expected + u * DL)) atomicMin(a.mismatch + c, static_cast<int32_t>(w));
   } else {
-    uint8_t *dst = a.out + u * DL;
-#pragma unroll
-    for (int j = 0; j < SW; j += 4) {
-      const uint4 v = make_uint4(o[j], o[j + 1], o[j + 2], o[j + 3]);
-      __builtin_memcpy(dst + 4 * j, &v, 16);
-      store_data_hold(v);
-    }
+    digest_store<A>(o, a.out + u * DL);
   }
 }
 
@@ -182,6 +203,123 @@ __global__ __launch_bounds__(kBlock) void digest_windows_coop(const DigestArgs a
   }
 }
 
+// ---- stripes: cells of two buffers, per-unit roles (DigestStripeArgs) ------------------------------------------------
+// The same two fetch forms over lanes (s, j, w) = (s * nunits + j) * nwin + w.  A wave's 64 windows lie in data and
+// coded units, several stripes and two allocations, so a window is named by its address, not by an offset from one
+// base.  The addresses are kept as integers and turned into pointers of the global address space where they are used:
+// that keeps every load a global_load (an address that went through LDS or a select would otherwise be a generic
+// pointer and load through flat_load, see coop_fetch).
+typedef const __attribute__((address_space(1))) uint8_t *gptr_t;
+
+struct StripeLane {
+  int64_t s, w, N;
+  uint64_t addr;  // of the window's first byte
+  DigestUnit un;
+};
+
+__device__ __forceinline__ StripeLane stripe_lane(const DigestStripeArgs &a, int64_t u) {
+  StripeLane l;
+  const int64_t c = u / a.nwin;
+  l.w = u - c * a.nwin;
+  l.s = c / a.nunits;
+  l.un = a.unit[c - l.s * a.nunits];
+  l.N = l.w == a.nwin - 1 ? a.len - l.w * a.bpc : a.bpc;
+  const uint64_t b0 = reinterpret_cast<uint64_t>(a.buf[0]), b1 = reinterpret_cast<uint64_t>(a.buf[1]);
+  l.addr = (l.un.buf ? b1 : b0) + static_cast<uint64_t>(l.un.off + l.s * (l.un.buf ? a.stripe_stride[1] : a.stripe_stride[0]) +
+                                                        l.w * a.bpc);
+  return l;
+}
+
+// the lane's digest: stored (compute units) or compared (verify units: the smallest slot * nwin + w per stripe)
+template <int A>
+__device__ __forceinline__ void stripe_result(const DigestStripeArgs &a, const StripeLane &l,
+                                              const uint32_t (&o)[dg::Traits<A>::kStateWords]) {
+  constexpr int DL = dg::Traits<A>::kDigestLen;
+  if (l.un.verify) {
+    const int64_t e = (l.s * a.exp_units + l.un.slot) * a.nwin + l.w;
+    if (digest_differs<A>(o, a.expected + e * DL))
+      atomicMin(a.mismatch + l.s, static_cast<int32_t>(l.un.slot * a.nwin + l.w));
+  } else {
+    digest_store<A>(o, a.out + ((l.s * a.out_units + l.un.slot) * a.nwin + l.w) * DL);
+  }
+}
+
+template <int A>
+__global__ __launch_bounds__(kBlock) void digest_stripes(const DigestStripeArgs a) {
+  const int64_t units = a.nstripes * a.nunits * a.nwin;
+  for (int64_t u = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; u < units;
+       u += static_cast<int64_t>(gridDim.x) * kBlock) {
+    const StripeLane l = stripe_lane(a, u);
+    const uint8_t *win = (const uint8_t *)reinterpret_cast<gptr_t>(l.addr);
+    uint32_t st[dg::Traits<A>::kStateWords], o[dg::Traits<A>::kStateWords];
+    dg::init<A>(st);
+    digest_blocks<A>(st, win, 0, l.N >> 6, l.N, o);
+    stripe_result<A>(a, l, o);
+  }
+}
+
+// coop_fetch with the stage holding the windows' addresses
+__device__ __forceinline__ void coop_fetch_addr(uint4 (&g)[16], const uint64_t *addrs, int sub, int col, int s) {
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
+    typedef const __attribute__((address_space(1))) u32x4u *vptr_t;
+    const u32x4u v = *reinterpret_cast<vptr_t>(addrs[4 * j + sub] + (static_cast<uint64_t>(s) << 8) + col);
+    g[j] = make_uint4(v[0], v[1], v[2], v[3]);
+  }
+}
+
+template <int A>
+__global__ __launch_bounds__(kBlock) void digest_stripes_coop(const DigestStripeArgs a) {
+  __shared__ __attribute__((aligned(16))) uint8_t s_mem[(kBlock / 64) * kCoopWave];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  uint8_t *stage = s_mem + wave * kCoopWave;
+  uint64_t *addrs = reinterpret_cast<uint64_t *>(stage + 64 * kCoopRow);
+  const int64_t units = a.nstripes * a.nunits * a.nwin;
+  for (int64_t u0 = (static_cast<int64_t>(blockIdx.x) * (kBlock / 64) + wave) * 64; u0 < units;
+       u0 += static_cast<int64_t>(gridDim.x) * kBlock) {
+    const bool live = u0 + lane < units;
+    StripeLane l = stripe_lane(a, live ? u0 + lane : u0);  // a dead lane names a window it never reads: no steps then
+    if (!live) l.N = 0;
+    const int64_t nb = l.N >> 6;
+    int steps = static_cast<int>(std::min<int64_t>(nb >> 2, 0x7fffffff));
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) steps = std::min(steps, __shfl_xor(steps, m, 64));
+    steps = __builtin_amdgcn_readfirstlane(steps);
+    uint32_t st[dg::Traits<A>::kStateWords];
+    dg::init<A>(st);
+    if (steps > 0) {
+      __builtin_amdgcn_wave_barrier();  // the previous unit's reads of `addrs` are done
+      addrs[lane] = l.addr;
+      __builtin_amdgcn_wave_barrier();
+      const int sub = lane >> 4, col = (lane & 15) * 16;
+      uint4 g[16];
+      coop_fetch_addr(g, addrs, sub, col, 0);
+      for (int s = 0; s < steps; ++s) {
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int j = 0; j < 16; ++j) *reinterpret_cast<uint4 *>(stage + (4 * j + sub) * kCoopRow + col) = g[j];
+        coop_fetch_addr(g, addrs, sub, col, std::min(s + 1, steps - 1));
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+        for (int b = 0; b < 4; ++b) {
+          uint32_t m[16];
+          __builtin_memcpy(m, stage + lane * kCoopRow + b * 64, 64);
+          dg::compress<A>(st, m);
+        }
+      }
+    }
+    if (live) {
+      const uint8_t *win = (const uint8_t *)reinterpret_cast<gptr_t>(l.addr);
+      uint32_t o[dg::Traits<A>::kStateWords];
+      digest_blocks<A>(st, win, static_cast<int64_t>(steps) << 2, nb, l.N, o);
+      stripe_result<A>(a, l, o);
+    }
+  }
+}
+
 // Which form a launch takes, from the A/B on 3,072 cells of 1 MiB (profiles/digest/): MD5, whose bound is the
 // fetch path, gains 11-12 % at 16 KiB windows and 36 % at 1 MiB windows from the cooperative form; SHA-256 is bound by
 // VALU issue and was 4 % slower with it (two waves per SIMD instead of three), so its cooperative instantiation is not
@@ -205,7 +343,26 @@ hipError_t launch(const DigestArgs &a, hipStream_t st) {
   return hipGetLastError();
 }
 
+template <int A>
+hipError_t launch_stripes(const DigestStripeArgs &a, hipStream_t st) {
+  const int64_t units = a.nstripes * a.nunits * a.nwin;
+  const dim3 grid(static_cast<unsigned>(std::min<int64_t>((units + kBlock - 1) / kBlock, int64_t{1} << 22)));
+  if constexpr (kCoop<A>) {
+    if (a.bpc >= 256) {
+      hipLaunchKernelGGL((digest_stripes_coop<A>), grid, dim3(kBlock), 0, st, a);
+      return hipGetLastError();
+    }
+  }
+  hipLaunchKernelGGL((digest_stripes<A>), grid, dim3(kBlock), 0, st, a);
+  return hipGetLastError();
+}
+
 }  // namespace
+
+hipError_t launch_digest_stripes(int algo, const DigestStripeArgs &a, hipStream_t stream) {
+  if (a.nstripes <= 0 || a.nunits <= 0 || a.nwin <= 0) return hipSuccess;
+  return algo == dg::kSha256 ? launch_stripes<dg::kSha256>(a, stream) : launch_stripes<dg::kMd5>(a, stream);
+}
 
 hipError_t launch_digest_windows(int algo, const DigestArgs &a, hipStream_t stream) {
   if (a.ncells <= 0 || a.nwin <= 0) return hipSuccess;

@@ -58,7 +58,7 @@ bool is_pinned(const void *p) {
 
 struct Pending {
   std::vector<uint8_t *> parity;  // caller's parity buffers (p of them)
-  uint32_t *crcs = nullptr;       // caller's CRC buffer or null
+  uint8_t *crcs = nullptr;        // caller's CRC / digest buffer or null
   bool parity_staged = false;     // parity comes back through staging (caller buffer not pinned)
 };
 
@@ -106,9 +106,9 @@ struct Batch {
   hipEvent_t copied = nullptr;   // recorded on the queue's H2D stream after this batch's last H2D copy
   hipEvent_t done = nullptr;
   uint8_t *d_units = nullptr;  // [S][k+rows][cell_len]
-  uint32_t *d_crcs = nullptr;  // [S][k+rows][nwin]
+  uint8_t *d_crcs = nullptr;   // [S][k+rows][nwin] window checksums of esz bytes (uint32 CRCs, SHA256 / MD5 digests)
   uint8_t *h_stage = nullptr;  // pinned [S][k+rows][cell_len], allocated on first pageable use
-  uint32_t *h_crcs = nullptr;  // pinned [S][k+rows][nwin]
+  uint8_t *h_crcs = nullptr;   // pinned [S][k+rows][nwin][esz]
   size_t n = 0, len = 0;
   uint64_t first_ticket = 0;
   bool in_flight = false;
@@ -123,6 +123,8 @@ struct ozec_stripe_queue {
   int node = -1;   // that node (its copy pool, copy_pool.hpp)
   int k = 0, p = 0, rows = 0, ctype = OZEC_CHECKSUM_NONE, big_endian = 0;
   size_t cell_len = 0, S = 0, bpc = 0, nwin_max = 0;
+  size_t esz = sizeof(uint32_t);  // bytes per window checksum: a uint32 CRC, or the digest length of SHA256 / MD5
+  bool digest() const { return ctype == OZEC_CHECKSUM_SHA256 || ctype == OZEC_CHECKSUM_MD5; }
   std::vector<Batch> batches;
   hipStream_t h2d = nullptr;  // every H2D copy, in submission order
   CopyRun h2d_run;            // H2D copies not issued yet (they extend while stripes arrive back to back)
@@ -161,10 +163,15 @@ struct ozec_stripe_queue {
     SQ_HIP(hipStreamWaitEvent(b.stream, b.copied, 0));
     if (ctype == OZEC_CHECKSUM_NONE) {
       if (int rc = ozec_encode_batch(enc, b.d_units, ss, us, d_par, ss, us, b.n, b.len, b.stream)) return rc;
+    } else if (digest()) {
+      // one coding launch and one digest launch per batch; digests per stripe [unit][window][digest length]
+      if (int rc = ozec_encode_digest_batch(enc, b.d_units, ss, us, d_par, ss, us, b.n, b.len, ctype, bpc, b.d_crcs,
+                                            b.stream))
+        return rc;
     } else {
       // CRC layout per stripe [unit][window] with a fixed stride of nw windows per unit
-      if (int rc = ozec_encode_crc_batch(enc, b.d_units, ss, us, d_par, ss, us, b.n, b.len, ctype, bpc, b.d_crcs,
-                                         big_endian, b.stream))
+      if (int rc = ozec_encode_crc_batch(enc, b.d_units, ss, us, d_par, ss, us, b.n, b.len, ctype, bpc,
+                                         reinterpret_cast<uint32_t *>(b.d_crcs), big_endian, b.stream))
         return rc;
     }
     // parity back: per stripe one copy per run of back-to-back parity cells, coalesced across stripes into 2D copies
@@ -187,8 +194,7 @@ struct ozec_stripe_queue {
     }
     SQ_HIP(d2h.issue(hipMemcpyDeviceToHost, b.stream));
     if (ctype != OZEC_CHECKSUM_NONE)
-      SQ_HIP(hipMemcpyAsync(b.h_crcs, b.d_crcs, b.n * units() * nw * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                            b.stream));
+      SQ_HIP(hipMemcpyAsync(b.h_crcs, b.d_crcs, b.n * units() * nw * esz, hipMemcpyDeviceToHost, b.stream));
     SQ_HIP(hipEventRecord(b.done, b.stream));
     b.in_flight = true;
     return OZEC_OK;
@@ -209,7 +215,7 @@ struct ozec_stripe_queue {
         }
       }
       if (pd.crcs && ctype != OZEC_CHECKSUM_NONE)
-        tasks.push_back({pd.crcs, b.h_crcs + i * units() * nw, units() * nw * sizeof(uint32_t)});
+        tasks.push_back({pd.crcs, b.h_crcs + i * units() * nw * esz, units() * nw * esz});
     }
     ozec::parallel_copy(tasks, ozec::CopyDir::kFromStaging, true, node);
     b.in_flight = false;
@@ -324,8 +330,8 @@ int ozec_stripe_queue_create(ozec_coder *enc, size_t cell_len, size_t stripes_pe
   if (is_dec) return set_error(OZEC_EINVAL, "not an encoder");
   if (cell_len == 0 || stripes_per_batch == 0) return set_error(OZEC_EINVAL, "cell_len and stripes_per_batch must be > 0");
   if (checksum_type != OZEC_CHECKSUM_NONE && checksum_type != OZEC_CHECKSUM_CRC32 &&
-      checksum_type != OZEC_CHECKSUM_CRC32C)
-    return set_error(OZEC_EINVAL, "checksum type must be NONE, CRC32 or CRC32C");
+      checksum_type != OZEC_CHECKSUM_CRC32C && ozec_digest_length(checksum_type) == 0)
+    return set_error(OZEC_EINVAL, "checksum type must be NONE, CRC32, CRC32C, SHA256 or MD5");
   if (checksum_type != OZEC_CHECKSUM_NONE && bpc == 0) return set_error(OZEC_EINVAL, "bytesPerChecksum must be positive");
   if (ozec_coder_is_closed(enc)) return set_error(OZEC_ECLOSED, "stripe queue: the encoder is closed");
   auto *q = new (std::nothrow) ozec_stripe_queue();
@@ -347,7 +353,8 @@ int ozec_stripe_queue_create(ozec_coder *enc, size_t cell_len, size_t stripes_pe
   q->rows = codec == OZEC_CODEC_XOR ? 1 : p;
   q->ctype = checksum_type;
   q->bpc = checksum_type == OZEC_CHECKSUM_NONE ? 0 : bpc;
-  q->big_endian = big_endian;
+  q->big_endian = big_endian;  // digests are byte strings: ignored for them
+  if (q->digest()) q->esz = ozec_digest_length(checksum_type);
   q->cell_len = cell_len;
   q->S = stripes_per_batch;
   q->nwin_max = q->nwin(cell_len);
@@ -361,8 +368,8 @@ int ozec_stripe_queue_create(ozec_coder *enc, size_t cell_len, size_t stripes_pe
     if (e == hipSuccess) e = hipEventCreateWithFlags(&b.done, hipEventDisableTiming);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b.d_units), q->S * q->stripe_bytes());
     if (e == hipSuccess && q->ctype != OZEC_CHECKSUM_NONE) {
-      e = hipMalloc(reinterpret_cast<void **>(&b.d_crcs), q->S * q->stripe_crcs() * sizeof(uint32_t));
-      if (e == hipSuccess && ozec::pinned_alloc(q->S * q->stripe_crcs() * sizeof(uint32_t), q->device,
+      e = hipMalloc(reinterpret_cast<void **>(&b.d_crcs), q->S * q->stripe_crcs() * q->esz);
+      if (e == hipSuccess && ozec::pinned_alloc(q->S * q->stripe_crcs() * q->esz, q->device,
                                                 reinterpret_cast<void **>(&b.h_crcs)) != 0)
         e = hipErrorOutOfMemory;
     }
@@ -375,10 +382,30 @@ int ozec_stripe_queue_create(ozec_coder *enc, size_t cell_len, size_t stripes_pe
   return OZEC_OK;
 }
 
+// ozec_stripe_queue_submit / _submit_digests: `sums` is the stripe's CRC or digest buffer, as the queue's type has it
+static int queue_submit(ozec_stripe_queue *q, const uint8_t *const *data, uint8_t *const *parity, size_t len,
+                        uint8_t *sums, uint64_t *ticket);
+
 int ozec_stripe_queue_submit(ozec_stripe_queue *q, const uint8_t *const *data, uint8_t *const *parity, size_t len,
                              uint32_t *crcs, uint64_t *ticket) {
   ozec::StatScope stat_(OZEC_OP_QUEUE, q ? static_cast<uint64_t>(q->k) * len : 0);
   if (!q) return set_error(OZEC_EINVAL, "null queue");
+  if (crcs && q->digest())
+    return set_error(OZEC_EINVAL, "this queue computes SHA256 / MD5 digests: submit with ozec_stripe_queue_submit_digests");
+  return queue_submit(q, data, parity, len, reinterpret_cast<uint8_t *>(crcs), ticket);
+}
+
+int ozec_stripe_queue_submit_digests(ozec_stripe_queue *q, const uint8_t *const *data, uint8_t *const *parity, size_t len,
+                                     uint8_t *digests, uint64_t *ticket) {
+  ozec::StatScope stat_(OZEC_OP_QUEUE, q ? static_cast<uint64_t>(q->k) * len : 0);
+  if (!q) return set_error(OZEC_EINVAL, "null queue");
+  if (!q->digest())
+    return set_error(OZEC_EINVAL, "this queue's checksum type is NONE or a CRC: submit with ozec_stripe_queue_submit");
+  return queue_submit(q, data, parity, len, digests, ticket);
+}
+
+static int queue_submit(ozec_stripe_queue *q, const uint8_t *const *data, uint8_t *const *parity, size_t len,
+                        uint8_t *crcs, uint64_t *ticket) {
   if (!data || !parity) return set_error(OZEC_EINVAL, "Invalid buffer found, not allowing null");
   for (int j = 0; j < q->k; ++j)
     if (!data[j]) return set_error(OZEC_EINVAL, "Invalid buffer found, not allowing null");

@@ -90,6 +90,8 @@ class StripeQueue:
         # CRCs cover the coded units: k data + p parity (XOR codes one parity row)
         self._units = self._k + (1 if encoder._config.get_codec() == "xor" else self._p)
         self._bpc = bytes_per_checksum if int(checksum_type) != int(ChecksumType.NONE) else 0
+        # SHA256 / MD5 queues deliver digests (submit(digests=...)) where the CRC queues deliver uint32 values
+        self._dl = int(L.lib().ozec_digest_length(int(checksum_type)))
         self._h = ctypes.c_void_p()
         rc = L.lib().ozec_stripe_queue_create(encoder._handle, cell_len, stripes_per_batch, int(checksum_type),
                                               bytes_per_checksum, 1 if big_endian else 0, ctypes.byref(self._h))
@@ -97,9 +99,10 @@ class StripeQueue:
             _raise_for(rc)
         self._held = collections.deque()  # (ticket, buffers) kept alive until their stripe completes
 
-    def submit(self, data, parity, length=None, crcs=None):
+    def submit(self, data, parity, length=None, crcs=None, digests=None):
         """data: k uint8 arrays, parity: p uint8 arrays (written when the stripe completes), crcs: optional
-        uint32 array of (k+p) * windows.  Returns the stripe's ticket."""
+        uint32 array of (k+p) * windows (CRC queues), digests: optional uint8 array of (k+p) * windows * digest
+        length bytes, laid out [unit][window][digest length] (SHA256 / MD5 queues).  Returns the stripe's ticket."""
         if len(data) != self._k or len(parity) != self._p:
             raise IllegalArgumentException("Invalid inputs/outputs length")
         n = length if length is not None else data[0].size
@@ -119,13 +122,26 @@ class StripeQueue:
                     or not crcs.flags.c_contiguous or not crcs.flags.writeable or crcs.size < need):
                 raise IllegalArgumentException(
                     f"Invalid crcs buffer: a writeable C-contiguous uint32 array of >= {need} elements is required")
+        if digests is not None:
+            if crcs is not None:
+                raise IllegalArgumentException("Invalid buffers: a stripe takes crcs or digests, not both")
+            need = self._units * (-(-n // self._bpc)) * self._dl if self._bpc else 0
+            if (not isinstance(digests, np.ndarray) or digests.dtype != np.uint8 or not digests.flags.c_contiguous
+                    or not digests.flags.writeable or digests.nbytes < need):
+                raise IllegalArgumentException(
+                    f"Invalid digests buffer: a writeable C-contiguous uint8 array of >= {need} bytes is required")
         t = ctypes.c_uint64()
-        rc = L.lib().ozec_stripe_queue_submit(self._h, L.ptr_array([a.ctypes.data for a in data]),
-                                              L.ptr_array([a.ctypes.data for a in parity]), n,
-                                              None if crcs is None else crcs.ctypes.data, ctypes.byref(t))
+        if digests is not None:
+            rc = L.lib().ozec_stripe_queue_submit_digests(self._h, L.ptr_array([a.ctypes.data for a in data]),
+                                                          L.ptr_array([a.ctypes.data for a in parity]), n,
+                                                          digests.ctypes.data, ctypes.byref(t))
+        else:
+            rc = L.lib().ozec_stripe_queue_submit(self._h, L.ptr_array([a.ctypes.data for a in data]),
+                                                  L.ptr_array([a.ctypes.data for a in parity]), n,
+                                                  None if crcs is None else crcs.ctypes.data, ctypes.byref(t))
         if rc != L.OZEC_OK:
             _raise_for(rc)
-        self._held.append((t.value, (list(data), list(parity), crcs)))
+        self._held.append((t.value, (list(data), list(parity), crcs, digests)))
         return t.value
 
     def state(self):

@@ -18,6 +18,17 @@ into the JSON afterwards:
   rocprofv3 --pmc FETCH_SIZE -d DIR -o run --output-format csv -- python scripts/digest_bench.py --pmc-kernels
   python scripts/digest_bench.py --merge-pmc DIR --out profiles/digest/digest_bench.json
 
+The stripe paths (ozec_encode_digest_batch and its host form, DESIGN 2.6 "stripes" and 3) have a run of their own:
+
+  python scripts/digest_bench.py --stripes [--out profiles/digest/stripe_digest_bench.json] [--reps 9]
+
+  device    rs-6-3, 1 MiB cells, 341 stripes, bpc 16 KiB and 1 MiB: ozec_encode_digest_batch against ozec_encode_batch
+            followed by ozec_digest_windows_batch over the uniform [S][k+p] layout, alternated in one loop
+  small     one queue batch (64 stripes) and one host chunk (32 stripes): the one-launch call, the same work with two
+            digest launches (data cells, parity cells), and the floor -- one lane's serial walk over one window
+  host      ozec_encode_digest_host_batch (SHA256, MD5) against ozec_encode_crc_host_batch (CRC32C) on one pinned batch,
+            alternated, bpc 16 KiB and 1 MiB
+
 There is no fallback: without a GPU the device, valu-rate and host sections fail.
 """
 import argparse
@@ -191,10 +202,12 @@ def merge_pmc(pmc_dir, out_path):
     per = {}
     for p in paths:
         for r in csv.DictReader(open(p)):
-            if "digest_windows" in r["Kernel_Name"] and r["Counter_Name"] == "FETCH_SIZE":
+            if (("digest_windows" in r["Kernel_Name"] or "digest_stripes" in r["Kernel_Name"])
+                    and r["Counter_Name"] == "FETCH_SIZE"):
                 per.setdefault(r["Kernel_Name"], []).append(float(r["Counter_Value"]))
     res = json.load(open(out_path))
-    alg = CELLS * CELL
+    # --pmc-kernels: 3,072 cells; --stripes-pmc-kernels: 341 stripes of 9 cells
+    alg = 341 * 9 * CELL if any("digest_stripes" in k for k in per) else CELLS * CELL
     res["hbm_traffic"] = {
         "source": "rocprofv3 --pmc FETCH_SIZE, counters only, one pass; bytes = 2 * FETCH_SIZE * 1024 on gfx950",
         "shape": f"{CELLS} cells of {CELL} bytes, bpc 16384", "algorithmic_bytes": alg,
@@ -274,6 +287,149 @@ def host_rows(reps):
     return rows, cross
 
 
+# ---- stripes: encode + digests in one call ---------------------------------------------------------------------------------
+
+def _alternate(fns, reps, warmup, timer):
+    """every function `warmup` times, then `reps` rounds in which each runs once, the order reversed every other round;
+    {name: [ms]}"""
+    for fn in fns.values():
+        for _ in range(warmup):
+            fn()
+    ms = {k: [] for k in fns}
+    order = list(fns)
+    for r in range(reps):
+        for k in (order if r % 2 == 0 else order[::-1]):  # no version always runs behind the same other one
+            ms[k].append(timer(fns[k]))
+    return ms
+
+
+def stripe_rows(reps, warmup):
+    import numpy as np
+    import torch
+    from devcopy import to_host
+    from ozone_amd import _lib as L
+    from ozone_amd import checksum as ck
+    from ozone_amd import rawcoder as rc
+    from ozone_amd.stripe_queue import host_alloc
+    assert torch.cuda.is_available(), "digest_bench needs a GPU"
+    lib = L.lib()
+    k, p, n = 6, 3, CELL
+    enc = rc.RawErasureEncoder(rc.ECReplicationConfig(k, p))
+
+    def ev(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def wall(fn):
+        t0 = time.perf_counter()
+        fn()
+        return (time.perf_counter() - t0) * 1e3
+    res = {"device_resident": [], "small_launches": [], "host": []}
+    S = 341
+    units = torch.empty(S * (k + p) * n, dtype=torch.uint8, device="cuda:0")
+    assert lib.ozec_fill_splitmix64_cells(units.data_ptr(), n, S * (k + p), n, 0xD16E57, 0, None) == 0
+    par = units[k * n:]
+    torch.cuda.synchronize()
+    for name, typ, dl, _ in ALGOS:
+        for bpc in (16384, 1 << 20):
+            nwin = n // bpc
+            dig = torch.zeros(S * (k + p) * nwin * dl, dtype=torch.uint8, device="cuda:0")
+            dig2 = torch.zeros_like(dig)
+
+            def one(dig=dig, bpc=bpc, typ=typ):
+                enc.encode_digest_batch(units, (k + p) * n, n, par, (k + p) * n, n, S, n, typ, bpc, dig)
+
+            def two(dig2=dig2, bpc=bpc, typ=typ):
+                enc.encode_batch(units, (k + p) * n, n, par, (k + p) * n, n, S, n)
+                ck.digest_windows_batch(typ, units, n, S * (k + p), n, bpc, dig2)
+            ms = _alternate({"encode_digest_batch": one, "encode_batch+digest_windows_batch": two},
+                            max(3, reps // 3) if bpc == 1 << 20 else reps, warmup, ev)
+            a, b = to_host(dig), to_host(dig2)
+            assert (a == b).all()  # same layout [S][k+p][nwin][dl]; spot check against hashlib below
+            u0 = to_host(units[:n]).tobytes()
+            assert a[:dl].tobytes() == hashlib.new(name, u0[:bpc]).digest()
+            row = {"algo": name, "bytes_per_checksum": bpc, "stripes": S, "cell_bytes": n, "schema": "rs-6-3",
+                   "ms": {c: spread(v) for c, v in ms.items()},
+                   "GBps_of_data": {c: S * k * n / (statistics.median(v) * 1e-3) / 1e9 for c, v in ms.items()}}
+            res["device_resident"].append(row)
+            print(json.dumps(row), flush=True)
+            del dig, dig2
+    # small launches, data and parity in two allocations as a queue batch / host chunk holds them
+    for name, typ, dl, _ in ALGOS:
+        bpc = 16384
+        nwin = n // bpc
+        one_win = torch.zeros(dl, dtype=torch.uint8, device="cuda:0")
+        for Ss, what in ((64, "queue batch"), (32, "host chunk")):
+            data = units[:Ss * k * n]
+            parity = torch.empty(Ss * p * n, dtype=torch.uint8, device="cuda:0")
+            dig = torch.zeros(Ss * (k + p) * nwin * dl, dtype=torch.uint8, device="cuda:0")
+            dd = torch.zeros(Ss * k * nwin * dl, dtype=torch.uint8, device="cuda:0")
+            dp = torch.zeros(Ss * p * nwin * dl, dtype=torch.uint8, device="cuda:0")
+            fns = {
+                "encode_digest_batch": lambda: enc.encode_digest_batch(data, k * n, n, parity, p * n, n, Ss, n, typ, bpc,
+                                                                       dig),
+                "encode_batch": lambda: enc.encode_batch(data, k * n, n, parity, p * n, n, Ss, n),
+                "encode_batch+two_digest_launches": lambda: (
+                    enc.encode_batch(data, k * n, n, parity, p * n, n, Ss, n),
+                    ck.digest_windows_batch(typ, data, n, Ss * k, n, bpc, dd),
+                    ck.digest_windows_batch(typ, parity, n, Ss * p, n, bpc, dp)),
+                "one_lane_one_window": lambda: ck.digest_windows_batch(typ, data, n, 1, bpc, bpc, one_win),
+            }
+            ms = _alternate(fns, reps, warmup, ev)
+            row = {"algo": name, "what": what, "stripes": Ss, "bytes_per_checksum": bpc, "lanes": Ss * (k + p) * nwin,
+                   "ms": {c: spread(v) for c, v in ms.items()}}
+            res["small_launches"].append(row)
+            print(json.dumps(row), flush=True)
+    del units, par
+    torch.cuda.empty_cache()
+    # from host memory: one pinned batch, CRC32C against the digests
+    Sh = 128
+    crc_bytes = Sh * (k + p) * (n // 16384) * 32
+    pool = host_alloc(Sh * (k + p) * n + crc_bytes + 4096)
+    h_in = pool.array[:Sh * k * n]
+    h_in.reshape(-1, 1 << 20)[:] = np.random.default_rng(3).integers(0, 256, 1 << 20, dtype=np.uint8)
+    h_out = pool.array[Sh * k * n:Sh * (k + p) * n]
+    h_sum = pool.array[Sh * (k + p) * n + 256:Sh * (k + p) * n + 256 + crc_bytes]
+    for bpc in (16384, 1 << 20):
+        fns = {"crc32c": lambda: enc.encode_crc_host_batch(h_in, k * n, n, h_out, p * n, n, Sh, n, 3, bpc,
+                                                           h_sum.ctypes.data)}
+        for name, typ, dl, _ in ALGOS:
+            fns[name] = lambda typ=typ: enc.encode_digest_host_batch(h_in, k * n, n, h_out, p * n, n, Sh, n, typ, bpc,
+                                                                     h_sum)
+        ms = _alternate(fns, max(3, reps // 2), 1, wall)
+        row = {"bytes_per_checksum": bpc, "stripes": Sh, "cell_bytes": n, "schema": "rs-6-3", "buffers": "pinned",
+               "stripes_per_chunk": 32, "ms": {c: spread(v) for c, v in ms.items()},
+               "GBps_of_data": {c: Sh * k * n / (statistics.median(v) * 1e-3) / 1e9 for c, v in ms.items()}}
+        res["host"].append(row)
+        print(json.dumps(row), flush=True)
+    del h_in, h_out, h_sum
+    pool.free()
+    return res
+
+
+def stripe_pmc_kernels():
+    """one encode_digest_batch per algorithm on the 341-stripe shape, for a counters-only pass (FETCH_SIZE of the stripe
+    kernels against the cell kernels' 1.013-1.016 of the algorithmic bytes)"""
+    import torch
+    from ozone_amd import _lib as L
+    from ozone_amd import rawcoder as rc
+    lib = L.lib()
+    k, p, n, S, bpc = 6, 3, CELL, 341, 16384
+    units = torch.empty(S * (k + p) * n, dtype=torch.uint8, device="cuda:0")
+    assert lib.ozec_fill_splitmix64_cells(units.data_ptr(), n, S * (k + p), n, 0xD16E57, 0, None) == 0
+    enc = rc.RawErasureEncoder(rc.ECReplicationConfig(k, p))
+    for name, typ, dl, _ in ALGOS:
+        dig = torch.zeros(S * (k + p) * (n // bpc) * dl, dtype=torch.uint8, device="cuda:0")
+        for _ in range(2):
+            enc.encode_digest_batch(units, (k + p) * n, n, units[k * n:], (k + p) * n, n, S, n, typ, bpc, dig)
+        torch.cuda.synchronize()
+    print("pmc kernels done")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "digest", "digest_bench.json"))
@@ -282,7 +438,19 @@ def main():
     ap.add_argument("--skip-host", action="store_true")
     ap.add_argument("--pmc-kernels", action="store_true", help="only launch each kernel (for a rocprofv3 --pmc pass)")
     ap.add_argument("--merge-pmc", metavar="DIR", help="merge a --pmc pass's counter CSV into --out")
+    ap.add_argument("--stripes", action="store_true", help="the stripe paths: encode + digests in one call")
+    ap.add_argument("--stripes-pmc-kernels", action="store_true", help="only launch the stripe kernels (for --pmc)")
     a = ap.parse_args()
+    if a.stripes_pmc_kernels:
+        return stripe_pmc_kernels()
+    if a.stripes:
+        out = a.out if a.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "digest",
+                                                                        "stripe_digest_bench.json")
+        res = stripe_rows(a.reps, a.warmup)
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        json.dump(res, open(out, "w"), indent=1)
+        print("wrote", out)
+        return
     if a.merge_pmc:
         return merge_pmc(a.merge_pmc, a.out)
     if a.pmc_kernels:
