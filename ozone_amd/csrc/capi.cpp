@@ -160,8 +160,8 @@ struct Slot {
   }
 };
 
-// End-to-end pipeline of ozec_encode_crc_host_batch: a ring of NB device chunk buffers; the chunk's H2D copies,
-// its kernel and its D2H copies go on three streams ordered by events, so the two copy directions and the
+// End-to-end pipeline of the host batches (run_chunk_ring below): a ring of NB device chunk buffers; the chunk's H2D
+// copies, its kernel and its D2H copies go on three streams ordered by events, so the two copy directions and the
 // kernel of consecutive chunks run at once.  One call at a time per device (mu).
 struct E2E {
   static constexpr int NB = 4;
@@ -238,6 +238,100 @@ struct SlotLease {
     if (slot) ctx->release(slot);
   }
 };
+
+// The chunk ring of a host batch on ctx's device: num_stripes stripes in chunks of C, chunk c through ring buffer
+// c % NB of dbytes (dbuf, and hstage when `staged`: some caller buffer is pageable).  The callers say what a chunk is,
+// each callable receiving (s0, cs, d, hs) -- first stripe, stripe count, device buffer, pinned staging or null:
+//   stage_in / stage_out: the host copies (CopyTask list, may be empty) into hs before, out of hs after the chunk
+//   h2d, launch, d2h: enqueue the chunk's copies up, its kernels and its copies back on P.h2d / P.comp / P.d2h
+// Everything else is here, once: no copy outlives the call, a ring buffer is refilled only after its previous chunk has
+// left the device, and the queues never hold more than NB chunks of commands.
+template <class StageIn, class H2D, class Launch, class D2H, class StageOut>
+int run_chunk_ring(DevCtx *ctx, size_t num_stripes, size_t C, size_t dbytes, bool staged, StageIn stage_in, H2D h2d,
+                   Launch launch, D2H d2h, StageOut stage_out) {
+  E2E &P = ctx->e2e;
+  constexpr size_t NB = E2E::NB;
+  std::lock_guard<std::mutex> lk(P.mu);
+  if (!P.h2d) {
+    OZEC_HIP(ozec::make_stream(&P.h2d));
+    OZEC_HIP(ozec::make_stream(&P.comp));
+    OZEC_HIP(ozec::make_stream(&P.d2h));
+    for (size_t b = 0; b < NB; ++b) {
+      OZEC_HIP(hipEventCreateWithFlags(&P.h2d_done[b], hipEventDisableTiming));
+      OZEC_HIP(hipEventCreateWithFlags(&P.comp_done[b], hipEventDisableTiming));
+      OZEC_HIP(hipEventCreateWithFlags(&P.d2h_done[b], hipEventDisableTiming));
+    }
+  }
+  // drain all three streams on every exit, so no copy of this call outlives it (error paths included)
+  struct DrainOnExit {
+    E2E &P;
+    ~DrainOnExit() {
+      (void)hipStreamSynchronize(P.h2d);
+      (void)hipStreamSynchronize(P.comp);
+      (void)hipStreamSynchronize(P.d2h);
+    }
+  } drain{P};
+  if (dbytes > P.dcap) {
+    for (auto &d : P.dbuf) {
+      if (d) (void)hipFree(d);
+      d = nullptr;
+    }
+    P.dcap = 0;
+    for (auto &d : P.dbuf) OZEC_HIP(hipMalloc(reinterpret_cast<void **>(&d), dbytes));
+    P.dcap = dbytes;
+  }
+  if (staged && dbytes > P.hcap) {
+    for (auto &h : P.hstage) {
+      if (h) (void)ozec::pinned_free(h);
+      h = nullptr;
+    }
+    P.hcap = 0;
+    for (auto &h : P.hstage)
+      if (ozec::pinned_alloc(dbytes, ctx->device, reinterpret_cast<void **>(&h)) != 0)
+        return fail(OZEC_ENOMEM, "cannot pin " + std::to_string(dbytes) + " bytes of staging memory");
+    P.hcap = dbytes;
+  }
+  const size_t nch = (num_stripes + C - 1) / C;
+  // host side of a finished, staged chunk c: its results from the staging buffer to the caller
+  auto unstage = [&](size_t c) -> int {
+    const size_t b = c % NB, s0 = c * C, cs = std::min(C, num_stripes - s0);
+    OZEC_HIP(hipEventSynchronize(P.d2h_done[b]));
+    ozec::parallel_copy(stage_out(s0, cs, P.dbuf[b], P.hstage[b]), ozec::CopyDir::kFromStaging, true, ctx->numa);
+    return OZEC_OK;
+  };
+  for (size_t c = 0; c < nch; ++c) {
+    const size_t b = c % NB, s0 = c * C, cs = std::min(C, num_stripes - s0);
+    uint8_t *d = P.dbuf[b], *hs = staged ? P.hstage[b] : nullptr;
+    if (staged) {
+      if (c >= NB)
+        if (int rc = unstage(c - NB)) return rc;  // frees hstage[b] for this chunk
+      ozec::parallel_copy(stage_in(s0, cs, d, hs), ozec::CopyDir::kToStaging, true, ctx->numa);
+    }
+    // H2D after the chunk that used this buffer NB chunks ago has left the device.  The host waits for it too
+    // (staged calls already did, in unstage): the HIP queues then never hold more than NB chunks of commands.
+    // Enqueuing a whole 8192-stripe batch up front (~40 commands per chunk) measured 27 GB/s at 16-stripe chunks
+    // against 49 GB/s for the same chunks of a 1024-stripe batch; with the wait, 45-48 GB/s at every size, and
+    // 56 GB/s (98 % of the 57.5 GB/s H2D link) with one rectangular copy per chunk and direction
+    // (scripts/e2e_probe2.py, profiles/r02/e2e_probe.log).
+    if (c >= NB) {
+      if (!staged) OZEC_HIP(hipEventSynchronize(P.d2h_done[b]));
+      OZEC_HIP(hipStreamWaitEvent(P.h2d, P.d2h_done[b], 0));
+    }
+    if (int rc = h2d(s0, cs, d, hs)) return rc;
+    OZEC_HIP(hipEventRecord(P.h2d_done[b], P.h2d));
+    OZEC_HIP(hipStreamWaitEvent(P.comp, P.h2d_done[b], 0));
+    if (int rc = launch(s0, cs, d, hs)) return rc;
+    OZEC_HIP(hipEventRecord(P.comp_done[b], P.comp));
+    OZEC_HIP(hipStreamWaitEvent(P.d2h, P.comp_done[b], 0));
+    if (int rc = d2h(s0, cs, d, hs)) return rc;
+    OZEC_HIP(hipEventRecord(P.d2h_done[b], P.d2h));
+  }
+  if (staged)
+    for (size_t c = nch > NB ? nch - NB : 0; c < nch; ++c)
+      if (int rc = unstage(c)) return rc;
+  OZEC_HIP(hipStreamSynchronize(P.d2h));
+  return OZEC_OK;
+}
 
 std::mutex g_ctx_mu;
 std::vector<std::unique_ptr<DevCtx>> g_ctx;
@@ -409,6 +503,64 @@ void encode_rows(const ozec_coder *enc, std::vector<uint8_t> &rows) {
 }
 
 int out_rows(const ozec_coder *enc) { return enc->codec == OZEC_CODEC_XOR ? 1 : enc->p; }
+
+// ---- setup shared by the device batch entry points
+
+// the batch fields of a coding launch: num_stripes stripes of len bytes per unit
+void fill_batch(CodeArgs &a, const uint8_t *d_in, int64_t in_stripe_stride, uint8_t *d_out, int64_t out_stripe_stride,
+                size_t num_stripes, size_t len) {
+  a.in = d_in;
+  a.out = d_out;
+  a.in_stripe_stride = in_stripe_stride;
+  a.out_stripe_stride = out_stripe_stride;
+  a.nstripes = static_cast<int64_t>(num_stripes);
+  a.len = static_cast<int64_t>(len);
+}
+
+// an encoder's coefficients, its data units at j * in_unit_stride and its coded rows at r * out_unit_stride
+void fill_encoder(CodeArgs &a, const ozec_coder *enc, int64_t in_unit_stride, int64_t out_unit_stride) {
+  const int k = enc->k, rows = out_rows(enc);
+  std::vector<uint8_t> coef;
+  encode_rows(enc, coef);
+  fill_coef(a, rows, k, coef.data());
+  for (int j = 0; j < k; ++j) a.in_off[j] = j * in_unit_stride;
+  for (int r = 0; r < rows; ++r) a.out_off[r] = r * out_unit_stride;
+}
+
+// a decoder's offsets: the units it reads at units[j] * in_unit_stride, its nrows coded outputs at r * out_unit_stride
+void fill_decoder_offsets(CodeArgs &a, const std::vector<int> &units, int64_t in_unit_stride, int nrows,
+                          int64_t out_unit_stride) {
+  for (size_t j = 0; j < units.size(); ++j) a.in_off[j] = units[j] * in_unit_stride;
+  for (int r = 0; r < nrows; ++r) a.out_off[r] = r * out_unit_stride;
+}
+
+// zero-fill outputs [first, last) of a batch: the outputs an XOR coder does not code (it codes outputs[0] only)
+int zero_outputs(uint8_t *d_out, int64_t out_stripe_stride, int64_t out_unit_stride, int first, int last, size_t len,
+                 size_t num_stripes, hipStream_t st) {
+  for (int r = first; r < last; ++r)
+    OZEC_HIP(hipMemset2DAsync(d_out + r * out_unit_stride, out_stripe_stride, 0, len, num_stripes, st));
+  return OZEC_OK;
+}
+
+// windows of bpc bytes per cell of len bytes (bpc == 0 is reported by the caller's other checks; it must not divide)
+size_t window_count(size_t len, size_t bpc) { return bpc ? (len + bpc - 1) / bpc : len; }
+
+// stripes per chunk of a host batch: the caller's, or the e2e_chunk knob
+size_t e2e_chunk_of(size_t stripes_per_chunk) {
+  return stripes_per_chunk ? stripes_per_chunk : static_cast<size_t>(std::max<int64_t>(1, ozec::g_tune.e2e_chunk.load()));
+}
+
+// the present-unit list of the batch decoders as one flag per unit
+int parse_present(const ozec_coder *dec, const int *present_units, int num_present, bool (&present)[256]) {
+  if (num_present < 0 || (num_present > 0 && !present_units)) return fail(OZEC_EINVAL, "invalid present units");
+  const int n_all = dec->k + dec->p;
+  std::fill(std::begin(present), std::end(present), false);
+  for (int i = 0; i < num_present; ++i) {
+    if (present_units[i] < 0 || present_units[i] >= n_all) return fail(OZEC_EINVAL, "present unit out of range");
+    present[present_units[i]] = true;
+  }
+  return OZEC_OK;
+}
 
 
 bool host_pinned(const void *p) {
@@ -921,24 +1073,12 @@ int ozec_encode_batch(ozec_coder *enc, const uint8_t *d_in, int64_t in_stripe_st
   if (!d_in || !d_out) return fail(OZEC_EINVAL, "Invalid buffer found, not allowing null");
   DevCtx *ctx;
   if (int rc = get_ctx(&ctx)) return rc;
-  const int k = enc->k, rows = out_rows(enc);
   CodeArgs a{};
-  a.in = d_in;
-  a.out = d_out;
-  a.in_stripe_stride = in_stripe_stride;
-  a.out_stripe_stride = out_stripe_stride;
-  a.nstripes = static_cast<int64_t>(num_stripes);
-  a.len = static_cast<int64_t>(len);
-  std::vector<uint8_t> coef;
-  encode_rows(enc, coef);
-  fill_coef(a, rows, k, coef.data());
-  for (int j = 0; j < k; ++j) a.in_off[j] = j * in_unit_stride;
-  for (int r = 0; r < rows; ++r) a.out_off[r] = r * out_unit_stride;
+  fill_batch(a, d_in, in_stripe_stride, d_out, out_stripe_stride, num_stripes, len);
+  fill_encoder(a, enc, in_unit_stride, out_unit_stride);
   hipStream_t st = pick_stream(ctx, stream);
   OZEC_HIP(ozec::launch_code(a, st));
-  for (int r = rows; r < enc->p; ++r)
-    OZEC_HIP(hipMemset2DAsync(d_out + r * out_unit_stride, out_stripe_stride, 0, len, num_stripes, st));
-  return OZEC_OK;
+  return zero_outputs(d_out, out_stripe_stride, out_unit_stride, a.rows, enc->p, len, num_stripes, st);
 }
 
 // ---- decode ------------------------------------------------------------------------------------
@@ -1095,12 +1235,8 @@ int ozec_decode_batch(ozec_coder *dec, const uint8_t *d_in, int64_t in_stripe_st
   ozec::StatScope stat_(OZEC_OP_DECODE_DEVICE, dec ? static_cast<uint64_t>(dec->k) * len * num_stripes : 0);
   if (int rc = check_open(dec, "decode")) return rc;
   if (!dec->decoder) return fail(OZEC_EINVAL, "not a decoder");
-  const int n_all = dec->k + dec->p;
-  bool present[256] = {false};
-  for (int i = 0; i < num_present; ++i) {
-    if (present_units[i] < 0 || present_units[i] >= n_all) return fail(OZEC_EINVAL, "present unit out of range");
-    present[present_units[i]] = true;
-  }
+  bool present[256];
+  if (int rc = parse_present(dec, present_units, num_present, present)) return rc;
   std::vector<int> units;
   std::vector<uint8_t> rows;
   if (int rc = plan_decode(dec, present, erased, n_erased, units, rows)) return rc;
@@ -1110,22 +1246,15 @@ int ozec_decode_batch(ozec_coder *dec, const uint8_t *d_in, int64_t in_stripe_st
   if (int rc = get_ctx(&ctx)) return rc;
   hipStream_t st = pick_stream(ctx, stream);
   CodeArgs a{};
-  a.in = d_in;
-  a.out = d_out;
-  a.in_stripe_stride = in_stripe_stride;
-  a.out_stripe_stride = out_stripe_stride;
-  a.nstripes = static_cast<int64_t>(num_stripes);
-  a.len = static_cast<int64_t>(len);
+  fill_batch(a, d_in, in_stripe_stride, d_out, out_stripe_stride, num_stripes, len);
   const int nin = static_cast<int>(units.size());
   if (dec->codec == OZEC_CODEC_XOR) fill_coef(a, 1, nin, rows.data());
   else fill_coef(a, n_erased, nin, rows.data());
   if (int rc = check_limits(a.k, a.rows)) return rc;
-  for (int j = 0; j < nin; ++j) a.in_off[j] = units[j] * in_unit_stride;
-  for (int r = 0; r < a.rows; ++r) a.out_off[r] = r * out_unit_stride;
+  fill_decoder_offsets(a, units, in_unit_stride, a.rows, out_unit_stride);
   OZEC_HIP(ozec::launch_code(a, st));
-  for (int r = a.rows; r < n_erased; ++r)
-    OZEC_HIP(hipMemset2DAsync(d_out + r * out_unit_stride, out_stripe_stride, 0, len, num_stripes, st));
-  return OZEC_OK;
+  // XOR decode: only erasedIndexes[0] is recovered, further outputs are zero-filled (XORRawDecoder.java:45-61)
+  return zero_outputs(d_out, out_stripe_stride, out_unit_stride, a.rows, n_erased, len, num_stripes, st);
 }
 
 // ---- checksums -----------------------------------------------------------------------------------
@@ -1171,7 +1300,7 @@ int ozec_checksum_windows_batch(int checksum_type, const uint8_t *d_base, int64_
   DevCtx *ctx;
   if (int rc = get_ctx(&ctx)) return rc;
   CrcArgs a;
-  const int64_t nwin = static_cast<int64_t>((len + (bpc ? bpc : 1) - 1) / (bpc ? bpc : 1));
+  const int64_t nwin = static_cast<int64_t>(window_count(len, bpc));
   if (int rc = make_crc_args(ctx, checksum_type, d_base, cell_stride, num_cells, len, bpc, d_out, nwin, big_endian, 0,
                              &a))
     return rc;
@@ -1291,18 +1420,9 @@ int ozec_encode_crc_batch(ozec_coder *enc, const uint8_t *d_in, int64_t in_strip
   const int k = enc->k, rows = out_rows(enc), units = k + rows;
   ozec::EncCrcArgs e{};
   CodeArgs &a = e.code;
-  a.in = d_in;
-  a.out = d_out;
-  a.in_stripe_stride = in_stripe_stride;
-  a.out_stripe_stride = out_stripe_stride;
-  a.nstripes = static_cast<int64_t>(num_stripes);
-  a.len = static_cast<int64_t>(len);
-  std::vector<uint8_t> coef;
-  encode_rows(enc, coef);
-  fill_coef(a, rows, k, coef.data());
-  for (int j = 0; j < k; ++j) a.in_off[j] = j * in_unit_stride;
-  for (int r = 0; r < rows; ++r) a.out_off[r] = r * out_unit_stride;
-  const int64_t nwin = static_cast<int64_t>((len + (bpc ? bpc : 1) - 1) / (bpc ? bpc : 1));
+  fill_batch(a, d_in, in_stripe_stride, d_out, out_stripe_stride, num_stripes, len);
+  fill_encoder(a, enc, in_unit_stride, out_unit_stride);
+  const int64_t nwin = static_cast<int64_t>(window_count(len, bpc));
   if (int rc = make_crc_args(ctx, checksum_type, nullptr, 0, num_stripes, len, bpc, d_crcs, nwin, big_endian, 0,
                              &e.crc))
     return rc;
@@ -1338,9 +1458,7 @@ int ozec_encode_crc_batch(ozec_coder *enc, const uint8_t *d_in, int64_t in_strip
   }
   // XOR with p > 1: every output is reset, only outputs[0] is coded (XORRawEncoder.java:67-85), as in
   // ozec_encode_batch; CRCs cover the coded units only
-  for (int r = rows; r < enc->p; ++r)
-    OZEC_HIP(hipMemset2DAsync(d_out + r * out_unit_stride, out_stripe_stride, 0, len, num_stripes, st));
-  return OZEC_OK;
+  return zero_outputs(d_out, out_stripe_stride, out_unit_stride, rows, enc->p, len, num_stripes, st);
 }
 
 int ozec_encode_crc_block_groups(ozec_coder *enc, uint8_t *d_base, int64_t group_stride, int64_t unit_stride,
@@ -1359,23 +1477,14 @@ int ozec_encode_crc_block_groups(ozec_coder *enc, uint8_t *d_base, int64_t group
   const int k = enc->k, rows = out_rows(enc), units = k + rows;
   const int64_t L = static_cast<int64_t>(len);
   uint8_t *d_par = d_base + static_cast<int64_t>(k) * unit_stride;
-  const int64_t nwin = static_cast<int64_t>((len + (bpc ? bpc : 1) - 1) / (bpc ? bpc : 1));
+  const int64_t nwin = static_cast<int64_t>(window_count(len, bpc));
   ozec::EncCrcArgs e{};
   CodeArgs &a = e.code;
-  a.in = d_base;
-  a.out = d_par;
-  a.in_stripe_stride = L;  // cells of one block are back to back
-  a.out_stripe_stride = L;
+  fill_batch(a, d_base, L, d_par, L, num_groups * stripes_per_group, len);  // cells of one block are back to back
   a.grp_stripes = static_cast<int64_t>(stripes_per_group);
   a.in_grp_stride = group_stride;
   a.out_grp_stride = group_stride;
-  a.nstripes = static_cast<int64_t>(num_groups * stripes_per_group);
-  a.len = L;
-  std::vector<uint8_t> coef;
-  encode_rows(enc, coef);
-  fill_coef(a, rows, k, coef.data());
-  for (int j = 0; j < k; ++j) a.in_off[j] = j * unit_stride;
-  for (int r = 0; r < rows; ++r) a.out_off[r] = r * unit_stride;
+  fill_encoder(a, enc, unit_stride, unit_stride);
   if (int rc = make_crc_args(ctx, checksum_type, nullptr, 0, a.nstripes, len, bpc, d_crcs, nwin, big_endian, 0, &e.crc))
     return rc;
   if (ozec::encode_crc_supported(a, static_cast<int64_t>(bpc))) {
@@ -1421,11 +1530,9 @@ static int encode_crc_host_batch_dev(ozec_coder *enc, const uint8_t *h_in, int64
   DevCtx *ctx;
   if (int rc = get_ctx(&ctx)) return rc;
   E2E &P = ctx->e2e;
-  std::lock_guard<std::mutex> lk(P.mu);
   const int k = enc->k, p = enc->p, rows = out_rows(enc), units = k + rows;
-  const size_t C = std::min(num_stripes, stripes_per_chunk ? stripes_per_chunk
-                                                          : static_cast<size_t>(std::max<int64_t>(1, ozec::g_tune.e2e_chunk.load())));
-  const size_t nwin = with_crc ? (len + bpc - 1) / bpc : 0;
+  const size_t C = std::min(num_stripes, e2e_chunk_of(stripes_per_chunk));
+  const size_t nwin = with_crc ? window_count(len, bpc) : 0;
   // device layout [C][k+p][dunit]: the unit pitch is the cell length (a key's last, partial stripe has any length,
   // ECKeyOutputStream.java:276).  Early in round 5 an odd pitch sent a 700,001-B stripe through the byte-wise kernels
   // (6.0 ms instead of 0.31 ms), so the pitch was rounded up to 16 B at the cost of a 2D copy per stripe; since the
@@ -1434,6 +1541,7 @@ static int encode_crc_host_batch_dev(ozec_coder *enc, const uint8_t *h_in, int64
   // (TuneKnobs::host_pitch16 = 1 restores the rounded pitch)
   const size_t dunit = ozec::g_tune.host_pitch16.load(std::memory_order_relaxed) ? round_up(len, 16) : len;
   const size_t dstripe = static_cast<size_t>(k + p) * dunit;
+  const size_t dpar = static_cast<size_t>(k) * dunit;                    // a stripe's parity cells in the device layout
   const size_t dcrc_off = round_up(C * dstripe, kStageAlign);            // then crcs [C][units][nwin]
   const size_t dbytes = dcrc_off + C * units * nwin * esz;
   const size_t ncrc = units * nwin * esz;                                // checksum bytes per stripe
@@ -1446,106 +1554,33 @@ static int encode_crc_host_batch_dev(ozec_coder *enc, const uint8_t *h_in, int64
   const bool out_pinned = range_pinned(h_out, out_span);
   const bool crc_pinned = !with_crc || range_pinned(h_crcs, num_stripes * ncrc);
   const bool staged = !in_pinned || !out_pinned || !crc_pinned;
-  if (!P.h2d) {
-    OZEC_HIP(ozec::make_stream(&P.h2d));
-    OZEC_HIP(ozec::make_stream(&P.comp));
-    OZEC_HIP(ozec::make_stream(&P.d2h));
-    for (int b = 0; b < E2E::NB; ++b) {
-      OZEC_HIP(hipEventCreateWithFlags(&P.h2d_done[b], hipEventDisableTiming));
-      OZEC_HIP(hipEventCreateWithFlags(&P.comp_done[b], hipEventDisableTiming));
-      OZEC_HIP(hipEventCreateWithFlags(&P.d2h_done[b], hipEventDisableTiming));
-    }
-  }
-  // drain all three streams on every exit, so no copy of this call outlives it (error paths included)
-  struct DrainOnExit {
-    E2E &P;
-    ~DrainOnExit() {
-      (void)hipStreamSynchronize(P.h2d);
-      (void)hipStreamSynchronize(P.comp);
-      (void)hipStreamSynchronize(P.d2h);
-    }
-  } drain{P};
-  if (dbytes > P.dcap) {
-    for (auto &d : P.dbuf) {
-      if (d) (void)hipFree(d);
-      d = nullptr;
-    }
-    P.dcap = 0;
-    for (auto &d : P.dbuf) OZEC_HIP(hipMalloc(reinterpret_cast<void **>(&d), dbytes));
-    P.dcap = dbytes;
-  }
-  if (staged && dbytes > P.hcap) {
-    for (auto &h : P.hstage) {
-      if (h) (void)ozec::pinned_free(h);
-      h = nullptr;
-    }
-    P.hcap = 0;
-    for (auto &h : P.hstage)
-      if (ozec::pinned_alloc(dbytes, ctx->device, reinterpret_cast<void **>(&h)) != 0)
-        return fail(OZEC_ENOMEM, "cannot pin " + std::to_string(dbytes) + " bytes of staging memory");
-    P.hcap = dbytes;
-  }
-  const size_t nch = (num_stripes + C - 1) / C;
-  // host side of chunk c: copy parity / CRCs of a finished, staged chunk to the caller
-  auto unstage = [&](size_t c) -> int {
-    const int b = static_cast<int>(c % E2E::NB);
-    OZEC_HIP(hipEventSynchronize(P.d2h_done[b]));
-    const size_t s0 = c * C, cs = std::min(C, num_stripes - s0);
+  const bool rect = ozec::g_tune.e2e_rect != 0;
+  auto stage_in = [&](size_t s0, size_t cs, uint8_t *, uint8_t *hs) {
     std::vector<ozec::CopyTask> tasks;
-    if (!out_pinned)
+    if (!in_pinned)
       for (size_t i = 0; i < cs; ++i)
-        for (int r = 0; r < p; ++r)
-          tasks.push_back({h_out + (s0 + i) * out_stripe_stride + r * out_unit_stride,
-                           P.hstage[b] + i * dstripe + static_cast<size_t>(k + r) * dunit, len});
-    if (with_crc && !crc_pinned)
-      tasks.push_back({h_crcs + s0 * ncrc, P.hstage[b] + dcrc_off, cs * ncrc});
-    ozec::parallel_copy(tasks, ozec::CopyDir::kFromStaging, true, ctx->numa);
-    return OZEC_OK;
+        for (int j = 0; j < k; ++j)
+          tasks.push_back({hs + i * dstripe + static_cast<size_t>(j) * dunit,
+                           h_in + (s0 + i) * in_stripe_stride + j * in_unit_stride, len});
+    return tasks;
   };
-  for (size_t c = 0; c < nch; ++c) {
-    const int b = static_cast<int>(c % E2E::NB);
-    const size_t s0 = c * C, cs = std::min(C, num_stripes - s0);
-    uint8_t *d = P.dbuf[b];
-    if (staged) {
-      if (c >= static_cast<size_t>(E2E::NB))
-        if (int rc = unstage(c - E2E::NB)) return rc;  // frees hstage[b] for this chunk
-      if (!in_pinned) {
-        std::vector<ozec::CopyTask> tasks;
-        for (size_t i = 0; i < cs; ++i)
-          for (int j = 0; j < k; ++j)
-            tasks.push_back({P.hstage[b] + i * dstripe + static_cast<size_t>(j) * dunit,
-                             h_in + (s0 + i) * in_stripe_stride + j * in_unit_stride, len});
-        ozec::parallel_copy(tasks, ozec::CopyDir::kToStaging, true, ctx->numa);
-      }
-    }
-    // H2D after the chunk that used this buffer NB chunks ago has left the device.  The host waits for it too
-    // (staged calls already did, in unstage): the HIP queues then never hold more than NB chunks of commands.
-    // Enqueuing a whole 8192-stripe batch up front (~40 commands per chunk) measured 27 GB/s at 16-stripe chunks
-    // against 49 GB/s for the same chunks of a 1024-stripe batch; with the wait, 45-48 GB/s at every size, and
-    // 56 GB/s (98 % of the 57.5 GB/s H2D link) with one rectangular copy per chunk and direction
-    // (scripts/e2e_probe2.py, profiles/r02/e2e_probe.log).
-    if (c >= static_cast<size_t>(E2E::NB)) {
-      if (!staged) OZEC_HIP(hipEventSynchronize(P.d2h_done[b]));
-      OZEC_HIP(hipStreamWaitEvent(P.h2d, P.d2h_done[b], 0));
-    }
-    const bool rect = ozec::g_tune.e2e_rect != 0;
+  auto h2d = [&](size_t s0, size_t cs, uint8_t *d, uint8_t *hs) -> int {
     if (!in_pinned) {
       // staged cells are already in the device layout: one copy of the data cells per stripe
       for (size_t i = 0; i < cs; ++i)
-        OZEC_HIP(hipMemcpyAsync(d + i * dstripe, P.hstage[b] + i * dstripe, static_cast<size_t>(k) * dunit,
-                                hipMemcpyHostToDevice, P.h2d));
+        OZEC_HIP(hipMemcpyAsync(d + i * dstripe, hs + i * dstripe, dpar, hipMemcpyHostToDevice, P.h2d));
     } else if (dunit != len) {
       for (size_t i = 0; i < cs; ++i)  // one rectangular copy per stripe: k rows of len bytes onto the unit pitch
         OZEC_HIP(hipMemcpy2DAsync(d + i * dstripe, dunit, h_in + (s0 + i) * in_stripe_stride,
                                   static_cast<size_t>(in_unit_stride), len, k, hipMemcpyHostToDevice, P.h2d));
     } else if (in_unit_stride == static_cast<int64_t>(len) && rect) {
       // one rectangular copy per chunk: cs rows of k*len bytes, source pitch = the batch's stripe stride
-      OZEC_HIP(hipMemcpy2DAsync(d, dstripe, h_in + s0 * in_stripe_stride, static_cast<size_t>(in_stripe_stride),
-                                static_cast<size_t>(k) * len, cs, hipMemcpyHostToDevice, P.h2d));
+      OZEC_HIP(hipMemcpy2DAsync(d, dstripe, h_in + s0 * in_stripe_stride, static_cast<size_t>(in_stripe_stride), dpar,
+                                cs, hipMemcpyHostToDevice, P.h2d));
     } else if (in_unit_stride == static_cast<int64_t>(len)) {
       for (size_t i = 0; i < cs; ++i)  // the k data cells of a stripe are one run
-        OZEC_HIP(hipMemcpyAsync(d + i * dstripe, h_in + (s0 + i) * in_stripe_stride, static_cast<size_t>(k) * len,
-                                hipMemcpyHostToDevice, P.h2d));
+        OZEC_HIP(hipMemcpyAsync(d + i * dstripe, h_in + (s0 + i) * in_stripe_stride, dpar, hipMemcpyHostToDevice,
+                                P.h2d));
     } else {
       for (size_t i = 0; i < cs; ++i)
         for (int j = 0; j < k; ++j)
@@ -1553,34 +1588,27 @@ static int encode_crc_host_batch_dev(ozec_coder *enc, const uint8_t *h_in, int64
                                   h_in + (s0 + i) * in_stripe_stride + j * in_unit_stride, len, hipMemcpyHostToDevice,
                                   P.h2d));
     }
-    OZEC_HIP(hipEventRecord(P.h2d_done[b], P.h2d));
-    OZEC_HIP(hipStreamWaitEvent(P.comp, P.h2d_done[b], 0));
+    return OZEC_OK;
+  };
+  auto launch = [&](size_t, size_t cs, uint8_t *d, uint8_t *) -> int {
     const int64_t ds = static_cast<int64_t>(dstripe), us = static_cast<int64_t>(dunit);
-    uint8_t *dcrc = d + dcrc_off;
-    if (digest) {
-      if (int rc = ozec_encode_digest_batch(enc, d, ds, us, d + static_cast<size_t>(k) * dunit, ds, us, cs, len,
-                                            checksum_type, bpc, dcrc, P.comp))
-        return rc;
-    } else if (with_crc) {
-      if (int rc = ozec_encode_crc_batch(enc, d, ds, us, d + static_cast<size_t>(k) * dunit, ds, us, cs, len,
-                                         checksum_type, bpc, reinterpret_cast<uint32_t *>(dcrc), big_endian, P.comp))
-        return rc;
-    } else {
-      if (int rc = ozec_encode_batch(enc, d, ds, us, d + static_cast<size_t>(k) * dunit, ds, us, cs, len, P.comp))
-        return rc;
-    }
-    OZEC_HIP(hipEventRecord(P.comp_done[b], P.comp));
-    OZEC_HIP(hipStreamWaitEvent(P.d2h, P.comp_done[b], 0));
-    uint8_t *hs = staged ? P.hstage[b] : nullptr;
+    if (digest)
+      return ozec_encode_digest_batch(enc, d, ds, us, d + dpar, ds, us, cs, len, checksum_type, bpc, d + dcrc_off,
+                                      P.comp);
+    if (with_crc)
+      return ozec_encode_crc_batch(enc, d, ds, us, d + dpar, ds, us, cs, len, checksum_type, bpc,
+                                   reinterpret_cast<uint32_t *>(d + dcrc_off), big_endian, P.comp);
+    return ozec_encode_batch(enc, d, ds, us, d + dpar, ds, us, cs, len, P.comp);
+  };
+  auto d2h = [&](size_t s0, size_t cs, uint8_t *d, uint8_t *hs) -> int {
     if (out_pinned && out_unit_stride == static_cast<int64_t>(len) && dunit == len && rect) {
-      OZEC_HIP(hipMemcpy2DAsync(h_out + s0 * out_stripe_stride, static_cast<size_t>(out_stripe_stride),
-                                d + static_cast<size_t>(k) * len, dstripe, static_cast<size_t>(p) * len, cs,
-                                hipMemcpyDeviceToHost, P.d2h));
+      OZEC_HIP(hipMemcpy2DAsync(h_out + s0 * out_stripe_stride, static_cast<size_t>(out_stripe_stride), d + dpar,
+                                dstripe, static_cast<size_t>(p) * len, cs, hipMemcpyDeviceToHost, P.d2h));
     } else for (size_t i = 0; i < cs; ++i) {
-      uint8_t *src = d + i * dstripe + static_cast<size_t>(k) * dunit;
+      uint8_t *src = d + i * dstripe + dpar;
       if (!out_pinned) {
-        OZEC_HIP(hipMemcpyAsync(hs + i * dstripe + static_cast<size_t>(k) * dunit, src, static_cast<size_t>(p) * dunit,
-                                hipMemcpyDeviceToHost, P.d2h));
+        OZEC_HIP(hipMemcpyAsync(hs + i * dstripe + dpar, src, static_cast<size_t>(p) * dunit, hipMemcpyDeviceToHost,
+                                P.d2h));
       } else if (dunit != len) {
         OZEC_HIP(hipMemcpy2DAsync(h_out + (s0 + i) * out_stripe_stride, static_cast<size_t>(out_unit_stride), src,
                                   dunit, len, p, hipMemcpyDeviceToHost, P.d2h));
@@ -1594,16 +1622,21 @@ static int encode_crc_host_batch_dev(ozec_coder *enc, const uint8_t *h_in, int64
       }
     }
     if (with_crc)
-      OZEC_HIP(hipMemcpyAsync(crc_pinned ? h_crcs + s0 * ncrc : hs + dcrc_off, dcrc, cs * ncrc, hipMemcpyDeviceToHost,
-                              P.d2h));
-    OZEC_HIP(hipEventRecord(P.d2h_done[b], P.d2h));
-  }
-  if (staged) {
-    for (size_t c = nch > static_cast<size_t>(E2E::NB) ? nch - E2E::NB : 0; c < nch; ++c)
-      if (int rc = unstage(c)) return rc;
-  }
-  OZEC_HIP(hipStreamSynchronize(P.d2h));
-  return OZEC_OK;
+      OZEC_HIP(hipMemcpyAsync(crc_pinned ? h_crcs + s0 * ncrc : hs + dcrc_off, d + dcrc_off, cs * ncrc,
+                              hipMemcpyDeviceToHost, P.d2h));
+    return OZEC_OK;
+  };
+  auto stage_out = [&](size_t s0, size_t cs, uint8_t *, uint8_t *hs) {
+    std::vector<ozec::CopyTask> tasks;
+    if (!out_pinned)
+      for (size_t i = 0; i < cs; ++i)
+        for (int r = 0; r < p; ++r)
+          tasks.push_back({h_out + (s0 + i) * out_stripe_stride + r * out_unit_stride,
+                           hs + i * dstripe + dpar + static_cast<size_t>(r) * dunit, len});
+    if (with_crc && !crc_pinned) tasks.push_back({h_crcs + s0 * ncrc, hs + dcrc_off, cs * ncrc});
+    return tasks;
+  };
+  return run_chunk_ring(ctx, num_stripes, C, dbytes, staged, stage_in, h2d, launch, d2h, stage_out);
 }
 
 // ---- batched verify and fused reconstruction -------------------------------
@@ -1621,7 +1654,7 @@ int ozec_checksum_verify_batch(int checksum_type, const uint8_t *d_base, int64_t
   if (len > 0) {
     if (!d_base || !d_expected) return fail(OZEC_EINVAL, "null buffer");
     CrcArgs a;
-    const int64_t nwin = static_cast<int64_t>((len + (bpc ? bpc : 1) - 1) / (bpc ? bpc : 1));
+    const int64_t nwin = static_cast<int64_t>(window_count(len, bpc));
     if (int rc = make_crc_args(ctx, checksum_type, d_base, cell_stride, num_cells, len, bpc, nullptr, nwin, 0, 0, &a))
       return rc;
     a.expected = d_expected;
@@ -1780,17 +1813,8 @@ int ozec_encode_digest_batch(ozec_coder *enc, const uint8_t *d_in, int64_t in_st
   if (int rc = get_ctx(&ctx)) return rc;
   hipStream_t st = pick_stream(ctx, stream);
   CodeArgs a{};
-  a.in = d_in;
-  a.out = d_out;
-  a.in_stripe_stride = in_stripe_stride;
-  a.out_stripe_stride = out_stripe_stride;
-  a.nstripes = static_cast<int64_t>(num_stripes);
-  a.len = static_cast<int64_t>(len);
-  std::vector<uint8_t> coef;
-  encode_rows(enc, coef);
-  fill_coef(a, rows, k, coef.data());
-  for (int j = 0; j < k; ++j) a.in_off[j] = j * in_unit_stride;
-  for (int r = 0; r < rows; ++r) a.out_off[r] = r * out_unit_stride;
+  fill_batch(a, d_in, in_stripe_stride, d_out, out_stripe_stride, num_stripes, len);
+  fill_encoder(a, enc, in_unit_stride, out_unit_stride);
   OZEC_HIP(ozec::launch_code(a, st));
   ozec::DigestStripeArgs g{};
   stripe_digest_shape(&g, num_stripes, len, bpc);
@@ -1808,9 +1832,7 @@ int ozec_encode_digest_batch(ozec_coder *enc, const uint8_t *d_in, int64_t in_st
   }
   OZEC_HIP(ozec::launch_digest_stripes(algo, g, st));
   // XOR with p > 1: every output is reset, only outputs[0] is coded, as in ozec_encode_batch
-  for (int r = rows; r < enc->p; ++r)
-    OZEC_HIP(hipMemset2DAsync(d_out + r * out_unit_stride, out_stripe_stride, 0, len, num_stripes, st));
-  return OZEC_OK;
+  return zero_outputs(d_out, out_stripe_stride, out_unit_stride, rows, enc->p, len, num_stripes, st);
 }
 
 int ozec_reconstruct_digest_batch(ozec_coder *dec, const uint8_t *d_in, int64_t in_stripe_stride, int64_t in_unit_stride,
@@ -1825,12 +1847,8 @@ int ozec_reconstruct_digest_batch(ozec_coder *dec, const uint8_t *d_in, int64_t 
   if (int rc = check_open(dec, "decode")) return rc;
   if (!dec->decoder) return fail(OZEC_EINVAL, "not a decoder");
   const int n_all = dec->k + dec->p;
-  if (num_present < 0 || (num_present > 0 && !present_units)) return fail(OZEC_EINVAL, "invalid present units");
-  bool present[256] = {false};
-  for (int i = 0; i < num_present; ++i) {
-    if (present_units[i] < 0 || present_units[i] >= n_all) return fail(OZEC_EINVAL, "present unit out of range");
-    present[present_units[i]] = true;
-  }
+  bool present[256];
+  if (int rc = parse_present(dec, present_units, num_present, present)) return rc;
   std::vector<int> units;
   std::vector<uint8_t> rows;
   if (int rc = plan_decode(dec, present, erased, n_erased, units, rows)) return rc;
@@ -1854,19 +1872,13 @@ int ozec_reconstruct_digest_batch(ozec_coder *dec, const uint8_t *d_in, int64_t 
   if (len > 0) {
     if (nrows) {
       CodeArgs a{};
-      a.in = d_in;
-      a.out = d_out;
-      a.in_stripe_stride = in_stripe_stride;
-      a.out_stripe_stride = out_stripe_stride;
-      a.nstripes = static_cast<int64_t>(num_stripes);
-      a.len = static_cast<int64_t>(len);
+      fill_batch(a, d_in, in_stripe_stride, d_out, out_stripe_stride, num_stripes, len);
       fill_coef(a, nrows, nin, rows.data());
-      for (int j = 0; j < nin; ++j) a.in_off[j] = units[j] * in_unit_stride;
-      for (int r = 0; r < nrows; ++r) a.out_off[r] = r * out_unit_stride;
+      fill_decoder_offsets(a, units, in_unit_stride, nrows, out_unit_stride);
       OZEC_HIP(ozec::launch_code(a, st));
     }
-    for (int r = nrows; r < n_erased; ++r)  // XOR decoders zero-fill outputs beyond erasedIndexes[0]
-      OZEC_HIP(hipMemset2DAsync(d_out + r * out_unit_stride, out_stripe_stride, 0, len, num_stripes, st));
+    // XOR decoders zero-fill outputs beyond erasedIndexes[0]
+    if (int rc = zero_outputs(d_out, out_stripe_stride, out_unit_stride, nrows, n_erased, len, num_stripes, st)) return rc;
     // one digest launch: the read units' lanes verify (only when stored digests were given), the rebuilt units' compute
     ozec::DigestStripeArgs g{};
     stripe_digest_shape(&g, num_stripes, len, bpc);
@@ -1910,11 +1922,8 @@ int ozec_reconstruct_crc_batch(ozec_coder *dec, const uint8_t *d_in, int64_t in_
   if (int rc = check_open(dec, "decode")) return rc;
   if (!dec->decoder) return fail(OZEC_EINVAL, "not a decoder");
   const int n_all = dec->k + dec->p;
-  bool present[256] = {false};
-  for (int i = 0; i < num_present; ++i) {
-    if (present_units[i] < 0 || present_units[i] >= n_all) return fail(OZEC_EINVAL, "present unit out of range");
-    present[present_units[i]] = true;
-  }
+  bool present[256];
+  if (int rc = parse_present(dec, present_units, num_present, present)) return rc;
   std::vector<int> units;
   std::vector<uint8_t> rows;
   if (int rc = plan_decode(dec, present, erased, n_erased, units, rows)) return rc;
@@ -1932,15 +1941,10 @@ int ozec_reconstruct_crc_batch(ozec_coder *dec, const uint8_t *d_in, int64_t in_
   }
   const int nin = static_cast<int>(units.size());
   const int nrows = dec->codec == OZEC_CODEC_XOR ? (n_erased ? 1 : 0) : n_erased;
-  const int64_t nwin = static_cast<int64_t>((len + (bpc ? bpc : 1) - 1) / (bpc ? bpc : 1));
+  const int64_t nwin = static_cast<int64_t>(window_count(len, bpc));
   ozec::EncCrcArgs e{};
   CodeArgs &a = e.code;
-  a.in = d_in;
-  a.out = d_out;
-  a.in_stripe_stride = in_stripe_stride;
-  a.out_stripe_stride = out_stripe_stride;
-  a.nstripes = static_cast<int64_t>(num_stripes);
-  a.len = static_cast<int64_t>(len);
+  fill_batch(a, d_in, in_stripe_stride, d_out, out_stripe_stride, num_stripes, len);
   if (nrows) {
     fill_coef(a, nrows, nin, rows.data());
     if (int rc = check_limits(a.k, a.rows)) return rc;
@@ -1948,8 +1952,7 @@ int ozec_reconstruct_crc_batch(ozec_coder *dec, const uint8_t *d_in, int64_t in_
     a.k = nin;
     a.rows = 0;
   }
-  for (int j = 0; j < nin; ++j) a.in_off[j] = units[j] * in_unit_stride;
-  for (int r = 0; r < nrows; ++r) a.out_off[r] = r * out_unit_stride;
+  fill_decoder_offsets(a, units, in_unit_stride, nrows, out_unit_stride);
   if (int rc = make_crc_args(ctx, checksum_type, nullptr, 0, num_stripes, len, bpc, d_out_crcs, nwin, out_big_endian, 0,
                              &e.crc))
     return rc;
@@ -1980,8 +1983,8 @@ int ozec_reconstruct_crc_batch(ozec_coder *dec, const uint8_t *d_in, int64_t in_
     if (nrows) OZEC_HIP(ozec::launch_code(a, st));
     // the rebuilt units' CRCs: one launch over all S x n_erased cells when they sit at one stride, else one per unit
     const bool uniform = out_stripe_stride == static_cast<int64_t>(n_erased) * out_unit_stride;
-    for (int r = nrows; r < n_erased && uniform; ++r)  // XOR decoders zero-fill outputs beyond erasedIndexes[0]
-      OZEC_HIP(hipMemset2DAsync(d_out + r * out_unit_stride, out_stripe_stride, 0, len, num_stripes, st));
+    // XOR decoders zero-fill outputs beyond erasedIndexes[0]
+    if (int rc = zero_outputs(d_out, out_stripe_stride, out_unit_stride, nrows, n_erased, len, num_stripes, st)) return rc;
     if (uniform && n_erased) {
       CrcArgs c = e.crc;
       c.base = d_out;
@@ -1993,9 +1996,6 @@ int ozec_reconstruct_crc_batch(ozec_coder *dec, const uint8_t *d_in, int64_t in_
       OZEC_HIP(ozec::launch_crc_windows(c, st));
     }
     for (int r = 0; r < n_erased && !uniform; ++r) {
-      if (r >= nrows) {  // XOR decoders zero-fill outputs beyond erasedIndexes[0]
-        OZEC_HIP(hipMemset2DAsync(d_out + r * out_unit_stride, out_stripe_stride, 0, len, num_stripes, st));
-      }
       CrcArgs c = e.crc;
       c.base = d_out + r * out_unit_stride;
       c.cell_stride = out_stripe_stride;
@@ -2010,10 +2010,9 @@ int ozec_reconstruct_crc_batch(ozec_coder *dec, const uint8_t *d_in, int64_t in_
 }
 
 // Fused reconstruction of stripes held in HOST memory: the datanode side of ECReconstructionCoordinator, whose read
-// buffers hold the k units it fetched (ECBlockReconstructedStripeInputStream.java:689-694).  The pipeline of
-// ozec_encode_crc_host_batch (ring of E2E::NB device chunk buffers, H2D / kernel / D2H on three streams, the host
-// waiting for a buffer's previous chunk before refilling it) around ozec_reconstruct_crc_batch.  Only the k units the
-// decoder reads cross PCIe, as one rectangular copy per run of consecutive unit indexes per chunk.
+// buffers hold the k units it fetched (ECBlockReconstructedStripeInputStream.java:689-694).  The chunk ring of
+// ozec_encode_crc_host_batch (run_chunk_ring) around ozec_reconstruct_crc_batch.  Only the k units the decoder reads
+// cross PCIe, as one rectangular copy per run of consecutive unit indexes per chunk.
 static int reconstruct_crc_host_batch_dev(ozec_coder *dec, const uint8_t *h_in, int64_t in_stripe_stride,
                                           int64_t in_unit_stride, const int *present_units, int num_present,
                                           const int *erased, int n_erased, uint8_t *h_out, int64_t out_stripe_stride,
@@ -2027,12 +2026,8 @@ static int reconstruct_crc_host_batch_dev(ozec_coder *dec, const uint8_t *h_in, 
   if (int rc = check_open(dec, "decode")) return rc;
   if (!dec->decoder) return fail(OZEC_EINVAL, "not a decoder");
   const int n_all = dec->k + dec->p;
-  if (num_present < 0 || (num_present > 0 && !present_units)) return fail(OZEC_EINVAL, "invalid present units");
-  bool present[256] = {false};
-  for (int i = 0; i < num_present; ++i) {
-    if (present_units[i] < 0 || present_units[i] >= n_all) return fail(OZEC_EINVAL, "present unit out of range");
-    present[present_units[i]] = true;
-  }
+  bool present[256];
+  if (int rc = parse_present(dec, present_units, num_present, present)) return rc;
   std::vector<int> units;
   std::vector<uint8_t> rows;
   if (int rc = plan_decode(dec, present, erased, n_erased, units, rows)) return rc;
@@ -2051,21 +2046,18 @@ static int reconstruct_crc_host_batch_dev(ozec_coder *dec, const uint8_t *h_in, 
   DevCtx *ctx;
   if (int rc = get_ctx(&ctx)) return rc;
   E2E &P = ctx->e2e;
-  std::lock_guard<std::mutex> lk(P.mu);
   const int e = n_erased;
-  const size_t C = std::min(num_stripes, stripes_per_chunk ? stripes_per_chunk
-                                                          : static_cast<size_t>(std::max<int64_t>(1, ozec::g_tune.e2e_chunk.load())));
-  const size_t nwin = (len + bpc - 1) / bpc;
+  const size_t C = std::min(num_stripes, e2e_chunk_of(stripes_per_chunk));
+  const size_t nwin = window_count(len, bpc);
+  const size_t nexp = static_cast<size_t>(n_all) * nwin * esz, nocrc = static_cast<size_t>(e) * nwin * esz;  // per stripe
   // device layout of one chunk buffer: input slots [C][k+p][len], rebuilt [C][e][len], expected CRCs [C][k+p][nwin],
-  // rebuilt CRCs [C][e][nwin], mismatch [C]
-  // 16-B aligned unit pitch, as in encode_crc_host_batch_dev
+  // rebuilt CRCs [C][e][nwin], mismatch [C]; the unit pitch as in encode_crc_host_batch_dev
   const size_t dunit = ozec::g_tune.host_pitch16.load(std::memory_order_relaxed) ? round_up(len, 16) : len;
   const size_t dstripe = static_cast<size_t>(n_all) * dunit, ostripe = static_cast<size_t>(e) * dunit;
   const size_t dout_off = round_up(C * dstripe, kStageAlign);
   const size_t dexp_off = round_up(dout_off + C * ostripe, kStageAlign);
-  const size_t dexp_bytes = h_expected ? C * n_all * nwin * esz : 0;
-  const size_t docrc_off = round_up(dexp_off + dexp_bytes, kStageAlign);
-  const size_t dmis_off = round_up(docrc_off + C * e * nwin * esz, kStageAlign);
+  const size_t docrc_off = round_up(dexp_off + (h_expected ? C * nexp : 0), kStageAlign);
+  const size_t dmis_off = round_up(docrc_off + C * nocrc, kStageAlign);
   const size_t dbytes = dmis_off + C * sizeof(int32_t);
   // runs of consecutive unit indexes among the units read: one rectangular copy per run and chunk
   std::vector<std::pair<int, int>> runs;
@@ -2081,87 +2073,21 @@ static int reconstruct_crc_host_batch_dev(ozec_coder *dec, const uint8_t *h_in, 
                             : 0;
   const bool in_pinned = range_pinned(h_in, in_span);
   const bool out_pinned = !e || range_pinned(h_out, out_span);
-  const bool exp_pinned = !h_expected || range_pinned(h_expected, num_stripes * n_all * nwin * esz);
-  const bool ocrc_pinned = !e || range_pinned(h_out_crcs, num_stripes * e * nwin * esz);
+  const bool exp_pinned = !h_expected || range_pinned(h_expected, num_stripes * nexp);
+  const bool ocrc_pinned = !e || range_pinned(h_out_crcs, num_stripes * nocrc);
   const bool mis_pinned = !h_expected || range_pinned(h_mismatch, num_stripes * sizeof(int32_t));
   const bool staged = !in_pinned || !out_pinned || !exp_pinned || !ocrc_pinned || !mis_pinned;
-  if (!P.h2d) {
-    OZEC_HIP(ozec::make_stream(&P.h2d));
-    OZEC_HIP(ozec::make_stream(&P.comp));
-    OZEC_HIP(ozec::make_stream(&P.d2h));
-    for (int b = 0; b < E2E::NB; ++b) {
-      OZEC_HIP(hipEventCreateWithFlags(&P.h2d_done[b], hipEventDisableTiming));
-      OZEC_HIP(hipEventCreateWithFlags(&P.comp_done[b], hipEventDisableTiming));
-      OZEC_HIP(hipEventCreateWithFlags(&P.d2h_done[b], hipEventDisableTiming));
-    }
-  }
-  struct DrainOnExit {
-    E2E &P;
-    ~DrainOnExit() {
-      (void)hipStreamSynchronize(P.h2d);
-      (void)hipStreamSynchronize(P.comp);
-      (void)hipStreamSynchronize(P.d2h);
-    }
-  } drain{P};
-  if (dbytes > P.dcap) {
-    for (auto &d : P.dbuf) {
-      if (d) (void)hipFree(d);
-      d = nullptr;
-    }
-    P.dcap = 0;
-    for (auto &d : P.dbuf) OZEC_HIP(hipMalloc(reinterpret_cast<void **>(&d), dbytes));
-    P.dcap = dbytes;
-  }
-  if (staged && dbytes > P.hcap) {
-    for (auto &h : P.hstage) {
-      if (h) (void)ozec::pinned_free(h);
-      h = nullptr;
-    }
-    P.hcap = 0;
-    for (auto &h : P.hstage)
-      if (ozec::pinned_alloc(dbytes, ctx->device, reinterpret_cast<void **>(&h)) != 0)
-        return fail(OZEC_ENOMEM, "cannot pin " + std::to_string(dbytes) + " bytes of staging memory");
-    P.hcap = dbytes;
-  }
-  const size_t nch = (num_stripes + C - 1) / C;
-  auto unstage = [&](size_t c) -> int {
-    const int b = static_cast<int>(c % E2E::NB);
-    OZEC_HIP(hipEventSynchronize(P.d2h_done[b]));
-    const size_t s0 = c * C, cs = std::min(C, num_stripes - s0);
+  auto stage_in = [&](size_t s0, size_t cs, uint8_t *, uint8_t *hs) {
     std::vector<ozec::CopyTask> tasks;
-    if (!out_pinned)
+    if (!in_pinned)
       for (size_t i = 0; i < cs; ++i)
-        for (int r = 0; r < e; ++r)
-          tasks.push_back({h_out + (s0 + i) * out_stripe_stride + r * out_unit_stride,
-                           P.hstage[b] + dout_off + i * ostripe + static_cast<size_t>(r) * dunit, len});
-    if (!ocrc_pinned)
-      tasks.push_back({h_out_crcs + s0 * e * nwin * esz, P.hstage[b] + docrc_off, cs * e * nwin * esz});
-    if (!mis_pinned) tasks.push_back({h_mismatch + s0, P.hstage[b] + dmis_off, cs * sizeof(int32_t)});
-    ozec::parallel_copy(tasks, ozec::CopyDir::kFromStaging, true, ctx->numa);
-    return OZEC_OK;
+        for (int u : units)
+          tasks.push_back({hs + i * dstripe + static_cast<size_t>(u) * dunit,
+                           h_in + (s0 + i) * in_stripe_stride + u * in_unit_stride, len});
+    if (!exp_pinned) tasks.push_back({hs + dexp_off, h_expected + s0 * nexp, cs * nexp});
+    return tasks;
   };
-  for (size_t c = 0; c < nch; ++c) {
-    const int b = static_cast<int>(c % E2E::NB);
-    const size_t s0 = c * C, cs = std::min(C, num_stripes - s0);
-    uint8_t *d = P.dbuf[b];
-    uint8_t *hs = staged ? P.hstage[b] : nullptr;
-    if (staged) {
-      if (c >= static_cast<size_t>(E2E::NB))
-        if (int rc = unstage(c - E2E::NB)) return rc;
-      std::vector<ozec::CopyTask> tasks;
-      if (!in_pinned)
-        for (size_t i = 0; i < cs; ++i)
-          for (int u : units)
-            tasks.push_back({hs + i * dstripe + static_cast<size_t>(u) * dunit,
-                             h_in + (s0 + i) * in_stripe_stride + u * in_unit_stride, len});
-      if (!exp_pinned)
-        tasks.push_back({hs + dexp_off, h_expected + s0 * n_all * nwin * esz, cs * n_all * nwin * esz});
-      ozec::parallel_copy(tasks, ozec::CopyDir::kToStaging, true, ctx->numa);
-    }
-    if (c >= static_cast<size_t>(E2E::NB)) {
-      if (!staged) OZEC_HIP(hipEventSynchronize(P.d2h_done[b]));
-      OZEC_HIP(hipStreamWaitEvent(P.h2d, P.d2h_done[b], 0));
-    }
+  auto h2d = [&](size_t s0, size_t cs, uint8_t *d, uint8_t *hs) -> int {
     for (const auto &run : runs) {
       const size_t off = static_cast<size_t>(run.first) * dunit, width = static_cast<size_t>(run.second) * dunit;
       if (!in_pinned) {
@@ -2183,27 +2109,23 @@ static int reconstruct_crc_host_batch_dev(ozec_coder *dec, const uint8_t *h_in, 
       }
     }
     if (h_expected)
-      OZEC_HIP(hipMemcpyAsync(d + dexp_off, exp_pinned ? h_expected + s0 * n_all * nwin * esz : hs + dexp_off,
-                              cs * n_all * nwin * esz, hipMemcpyHostToDevice, P.h2d));
-    OZEC_HIP(hipEventRecord(P.h2d_done[b], P.h2d));
-    OZEC_HIP(hipStreamWaitEvent(P.comp, P.h2d_done[b], 0));
-    if (digest) {
-      if (int rc = ozec_reconstruct_digest_batch(
-              dec, d, static_cast<int64_t>(dstripe), static_cast<int64_t>(dunit), present_units, num_present, erased, e,
-              d + dout_off, static_cast<int64_t>(ostripe), static_cast<int64_t>(dunit), cs, len, checksum_type, bpc,
-              h_expected ? d + dexp_off : nullptr, d + docrc_off,
-              h_expected ? reinterpret_cast<int32_t *>(d + dmis_off) : nullptr, P.comp))
-        return rc;
-    } else if (int rc = ozec_reconstruct_crc_batch(
-                   dec, d, static_cast<int64_t>(dstripe), static_cast<int64_t>(dunit), present_units, num_present, erased,
-                   e, d + dout_off, static_cast<int64_t>(ostripe), static_cast<int64_t>(dunit), cs, len, checksum_type,
-                   bpc, h_expected ? reinterpret_cast<const uint32_t *>(d + dexp_off) : nullptr, expected_big_endian,
-                   reinterpret_cast<uint32_t *>(d + docrc_off), out_big_endian,
-                   h_expected ? reinterpret_cast<int32_t *>(d + dmis_off) : nullptr, P.comp)) {
-      return rc;
-    }
-    OZEC_HIP(hipEventRecord(P.comp_done[b], P.comp));
-    OZEC_HIP(hipStreamWaitEvent(P.d2h, P.comp_done[b], 0));
+      OZEC_HIP(hipMemcpyAsync(d + dexp_off, exp_pinned ? h_expected + s0 * nexp : hs + dexp_off, cs * nexp,
+                              hipMemcpyHostToDevice, P.h2d));
+    return OZEC_OK;
+  };
+  auto launch = [&](size_t, size_t cs, uint8_t *d, uint8_t *) -> int {
+    const int64_t ds = static_cast<int64_t>(dstripe), os = static_cast<int64_t>(ostripe), us = static_cast<int64_t>(dunit);
+    uint8_t *dexp = h_expected ? d + dexp_off : nullptr;
+    int32_t *dmis = h_expected ? reinterpret_cast<int32_t *>(d + dmis_off) : nullptr;
+    if (digest)
+      return ozec_reconstruct_digest_batch(dec, d, ds, us, present_units, num_present, erased, e, d + dout_off, os, us,
+                                           cs, len, checksum_type, bpc, dexp, d + docrc_off, dmis, P.comp);
+    return ozec_reconstruct_crc_batch(dec, d, ds, us, present_units, num_present, erased, e, d + dout_off, os, us, cs,
+                                      len, checksum_type, bpc, reinterpret_cast<const uint32_t *>(dexp),
+                                      expected_big_endian, reinterpret_cast<uint32_t *>(d + docrc_off), out_big_endian,
+                                      dmis, P.comp);
+  };
+  auto d2h = [&](size_t s0, size_t cs, uint8_t *d, uint8_t *hs) -> int {
     if (e) {
       if (!out_pinned) {
         OZEC_HIP(hipMemcpyAsync(hs + dout_off, d + dout_off, cs * ostripe, hipMemcpyDeviceToHost, P.d2h));
@@ -2221,19 +2143,26 @@ static int reconstruct_crc_host_batch_dev(ozec_coder *dec, const uint8_t *h_in, 
                                     d + dout_off + i * ostripe + static_cast<size_t>(r) * len, len, hipMemcpyDeviceToHost,
                                     P.d2h));
       }
-      OZEC_HIP(hipMemcpyAsync(ocrc_pinned ? h_out_crcs + s0 * e * nwin * esz : hs + docrc_off, d + docrc_off,
-                              cs * e * nwin * esz, hipMemcpyDeviceToHost, P.d2h));
+      OZEC_HIP(hipMemcpyAsync(ocrc_pinned ? h_out_crcs + s0 * nocrc : hs + docrc_off, d + docrc_off, cs * nocrc,
+                              hipMemcpyDeviceToHost, P.d2h));
     }
     if (h_expected)
       OZEC_HIP(hipMemcpyAsync(mis_pinned ? reinterpret_cast<uint8_t *>(h_mismatch + s0) : hs + dmis_off, d + dmis_off,
                               cs * sizeof(int32_t), hipMemcpyDeviceToHost, P.d2h));
-    OZEC_HIP(hipEventRecord(P.d2h_done[b], P.d2h));
-  }
-  if (staged) {
-    for (size_t c = nch > static_cast<size_t>(E2E::NB) ? nch - E2E::NB : 0; c < nch; ++c)
-      if (int rc = unstage(c)) return rc;
-  }
-  OZEC_HIP(hipStreamSynchronize(P.d2h));
+    return OZEC_OK;
+  };
+  auto stage_out = [&](size_t s0, size_t cs, uint8_t *, uint8_t *hs) {
+    std::vector<ozec::CopyTask> tasks;
+    if (!out_pinned)
+      for (size_t i = 0; i < cs; ++i)
+        for (int r = 0; r < e; ++r)
+          tasks.push_back({h_out + (s0 + i) * out_stripe_stride + r * out_unit_stride,
+                           hs + dout_off + i * ostripe + static_cast<size_t>(r) * dunit, len});
+    if (!ocrc_pinned) tasks.push_back({h_out_crcs + s0 * nocrc, hs + docrc_off, cs * nocrc});
+    if (!mis_pinned) tasks.push_back({h_mismatch + s0, hs + dmis_off, cs * sizeof(int32_t)});
+    return tasks;
+  };
+  if (int rc = run_chunk_ring(ctx, num_stripes, C, dbytes, staged, stage_in, h2d, launch, d2h, stage_out)) return rc;
   if (!h_expected && h_mismatch)
     for (size_t s = 0; s < num_stripes; ++s) h_mismatch[s] = -1;
   return OZEC_OK;
@@ -2297,10 +2226,6 @@ static int host_batch_split(const ozec_coder *c, size_t num_stripes, size_t chun
 }
 
 extern "C" {
-
-static size_t e2e_chunk_of(size_t stripes_per_chunk) {
-  return stripes_per_chunk ? stripes_per_chunk : static_cast<size_t>(std::max<int64_t>(1, ozec::g_tune.e2e_chunk.load()));
-}
 
 int ozec_encode_crc_host_batch(ozec_coder *enc, const uint8_t *h_in, int64_t in_stripe_stride,
                                int64_t in_unit_stride, uint8_t *h_out, int64_t out_stripe_stride,

@@ -53,7 +53,7 @@ def _check(v, crcs, codec, k, p, n, S, ctype, bpc, big_endian=False):
 
 @pytest.mark.parametrize("pinned", [True, False])
 @pytest.mark.parametrize("codec,k,p,n,S,chunk,ctype,bpc", [
-    ("rs", 6, 3, 1 << 16, 37, 8, ck.ChecksumType.CRC32C, 16384),   # 5 chunks through a ring of 3
+    ("rs", 6, 3, 1 << 16, 37, 8, ck.ChecksumType.CRC32C, 16384),   # 5 chunks through a ring of 4
     ("rs", 6, 3, 1 << 20, 5, 0, ck.ChecksumType.CRC32C, 16384),    # C5 cells, default chunking
     ("rs", 10, 4, 50000, 7, 2, ck.ChecksumType.CRC32, 4096),       # unfused fallback shape (len % 16 != 0)
     ("rs", 3, 2, 1 << 15, 9, 4, ck.ChecksumType.NONE, 0),          # encode only
@@ -241,6 +241,29 @@ def test_reconstruct_host_batch_errors():
     with pytest.raises(rc.IllegalArgumentException):  # too many erased
         dec.reconstruct_crc_host_batch(buf, 9 * 4096, 4096, [4, 5, 6, 7, 8, 3], [0, 1, 2, 3], np.zeros(4 * 4096, np.uint8),
                                        4 * 4096, 4096, 1, 4096, ck.ChecksumType.CRC32C, 4096, np.zeros(4, np.uint32))
+    # a present list that cannot be read (null with a positive count, or a negative count) is an argument error of
+    # the CRC-typed calls as of the digest ones: OZEC_EINVAL before anything is written
+    from devcopy import to_dev, to_host
+    lib, h, n, C = L.lib(), dec._handle, 4096, int(ck.ChecksumType.CRC32C)
+    erased = L.int_array([0])
+    d_in = to_dev(buf)
+    for num_present in (3, -1):
+        present = None if num_present > 0 else L.int_array(list(range(1, 9)))
+        d_out, d_crc, d_mis = (to_dev(np.full(x, 0xA5, np.uint8)) for x in (n, 4, 4))
+        assert lib.ozec_decode_batch(h, d_in.data_ptr(), 9 * n, n, present, num_present, erased, 1, d_out.data_ptr(),
+                                     n, n, 1, n, None) == L.OZEC_EINVAL
+        assert L.last_error() == "invalid present units"
+        assert lib.ozec_reconstruct_crc_batch(h, d_in.data_ptr(), 9 * n, n, present, num_present, erased, 1,
+                                              d_out.data_ptr(), n, n, 1, n, C, n, None, 0, d_crc.data_ptr(), 0,
+                                              d_mis.data_ptr(), None) == L.OZEC_EINVAL
+        assert L.last_error() == "invalid present units"
+        assert all((to_host(x) == 0xA5).all() for x in (d_out, d_crc, d_mis))
+        h_out, h_crc, h_mis = (np.full(x, 0xA5, np.uint8) for x in (n, 4, 4))
+        assert lib.ozec_reconstruct_crc_host_batch(h, buf.ctypes.data, 9 * n, n, present, num_present, erased, 1,
+                                                   h_out.ctypes.data, n, n, 1, n, C, n, None, 0, h_crc.ctypes.data, 0,
+                                                   h_mis.ctypes.data, 0) == L.OZEC_EINVAL
+        assert L.last_error() == "invalid present units"
+        assert all((x == 0xA5).all() for x in (h_out, h_crc, h_mis))
 
 
 _REGISTERED_KEEP = []  # OZEC_TEST_KEEP_REGISTERED=1: the round 4-5 workaround, registered ranges mapped until exit
@@ -489,3 +512,155 @@ def _odd_host_batches(n, pinned):
         if keep is not None:
             del v, buf
             keep.free()
+
+
+# ------------------------------------------------------------------ every copy form of the host batches' chunk ring
+
+# rs-3-2, 11 stripes in chunks of 2: six chunks through the ring of 4 (two buffers are refilled, the last chunk holds
+# one stripe); cells of 4 or 5 windows, the odd length ending in a 3-byte window
+_RK, _RP, _RS, _RCHUNK, _RBPC = 3, 2, 11, 2, 1024
+_RING_REF = {}
+
+
+def _ring_ref(n):
+    """Read-only reference per cell length: units [S][k+p][n] (data from the generator, parity from the oracle) and
+    their CRC32C windows [S][k+p][nwin]."""
+    if n not in _RING_REF:
+        units = np.empty((_RS, _RK + _RP, n), np.uint8)
+        for s in range(_RS):
+            d = cells(SEED, 840000 + s * _RK, _RK, n)
+            units[s] = np.stack(d + oracle.rs_encode(_RK, _RP, d))
+        crcs = np.stack([np.stack([oracle.crc_windows(oracle.CRC32C, units[s, u], _RBPC) for u in range(_RK + _RP)])
+                         for s in range(_RS)]).astype(np.uint32)
+        units.setflags(write=False)
+        crcs.setflags(write=False)
+        _RING_REF[n] = units, crcs
+    return _RING_REF[n]
+
+
+def _placed(a, pinned, keep):
+    """A copy of the uint8 array `a`, flat, in host_alloc memory ('P') or in a plain numpy array ('U')."""
+    if pinned != "P":
+        return a.reshape(-1).copy()
+    pb = host_alloc(a.size)
+    keep.append(pb)
+    pb.array[:] = a.reshape(-1)
+    return pb.array
+
+
+def _ring_encode(n, gap, pins, rect, ctype=ck.ChecksumType.CRC32C):
+    """One encode host batch with parity and checksums in buffers of their own; pins = 'P'/'U' for (input, output,
+    checksums)."""
+    k, p, S, bpc = _RK, _RP, _RS, _RBPC
+    units, crcs = _ring_ref(n)
+    us, nwin = n + gap, -(-n // bpc)
+    esz = {ck.ChecksumType.NONE: 0, ck.ChecksumType.CRC32C: 4, ck.ChecksumType.SHA256: 32}[ctype]
+    src = np.full((S, k, us), 0xA5, np.uint8)
+    src[:, :, :n] = units[:, :k]
+    keep = []
+    h_in = _placed(src, pins[0], keep)
+    h_out = _placed(np.full(S * p * us, 0xA5, np.uint8), pins[1], keep)
+    h_ck = _placed(np.full(max(1, S * (k + p) * nwin * esz), 0xA5, np.uint8), pins[2], keep)
+    lib = L.lib()
+    enc = rc.RawErasureEncoder(rc.ECReplicationConfig(k, p))
+    assert lib.ozec_set_tuning(b"e2e_rect", rect) == 0
+    try:
+        if ctype == ck.ChecksumType.SHA256:
+            enc.encode_digest_host_batch(h_in, k * us, us, h_out, p * us, us, S, n, ctype, bpc, h_ck, _RCHUNK)
+        else:
+            enc.encode_crc_host_batch(h_in, k * us, us, h_out, p * us, us, S, n, ctype, bpc,
+                                      h_ck if esz else None, False, _RCHUNK)
+    finally:
+        lib.ozec_set_tuning(b"e2e_rect", 1)
+    what = (n, gap, pins, rect, ctype)
+    assert (h_in.reshape(S, k, us) == src).all(), what                    # the input, its gaps included
+    out = h_out.reshape(S, p, us)
+    assert (out[:, :, :n] == units[:, k:]).all(), what                    # parity equals the oracle
+    assert (out[:, :, n:] == 0xA5).all(), what                            # bytes past each cell are untouched
+    if ctype == ck.ChecksumType.CRC32C:
+        assert (h_ck.view(np.uint32).reshape(S, k + p, nwin) == crcs).all(), what
+    elif ctype == ck.ChecksumType.SHA256:
+        import hashlib
+        got = h_ck.reshape(S, k + p, nwin, 32)
+        for s in range(S):
+            for u in range(k + p):
+                for w in range(nwin):
+                    ref = hashlib.sha256(units[s, u, w * bpc:(w + 1) * bpc].tobytes()).digest()
+                    assert got[s, u, w].tobytes() == ref, what + (s, u, w)
+    else:
+        assert (h_ck == 0xA5).all(), what
+    for pb in keep:
+        pb.free()
+
+
+@pytest.mark.parametrize("gap", [0, 5])
+@pytest.mark.parametrize("n", [4096, 4099])
+def test_host_batch_ring_encode_forms(n, gap):
+    """ozec_encode_crc_host_batch with parity and checksums in buffers of their own, every mix of pinned and pageable
+    input / output / checksums that takes another copy form, with one rectangular copy per chunk (e2e_rect = 1) and
+    without: parity and CRC32C equal the oracle, nothing else is written."""
+    for pins in ("PPP", "PUU", "UPP", "PPU", "UUU"):
+        for rect in (0, 1):
+            _ring_encode(n, gap, pins, rect)
+
+
+def test_host_batch_ring_encode_other_checksum_types():
+    """The same ring without checksums (NONE) and with SHA256 window digests (ozec_encode_digest_host_batch, 32-byte
+    elements, against hashlib), pinned input and pageable outputs."""
+    _ring_encode(4099, 0, "PUU", 1, ck.ChecksumType.NONE)
+    _ring_encode(4099, 5, "PUU", 1, ck.ChecksumType.SHA256)
+
+
+def _ring_reconstruct(n, gap, erased, pins, verify=True):
+    """One reconstruct host batch; pins = 'P'/'U' for (input, output, expected, rebuilt checksums, mismatch)."""
+    k, p, S, bpc = _RK, _RP, _RS, _RBPC
+    units, crcs = _ring_ref(n)
+    us, nwin, e = n + gap, -(-n // bpc), len(erased)
+    present = [u for u in range(k + p) if u not in erased]
+    read = present[:k]
+    src = np.full((S, k + p, us), 0xA5, np.uint8)
+    src[:, :, :n] = units
+    src[:, erased, :] = 0xEE                   # erased units hold garbage in the caller's buffers
+    bad = 2
+    src[bad, read[-1], 2 * bpc + 5] ^= 0x01    # one corrupted window in the last unit read of one stripe
+    keep = []
+    h_in = _placed(src, pins[0], keep)
+    h_out = _placed(np.full(S * e * n, 0xA5, np.uint8), pins[1], keep)
+    h_exp = _placed(crcs.view(np.uint8), pins[2], keep).view(np.uint32) if verify else None
+    h_ocrc = _placed(np.full(S * e * nwin * 4, 0xA5, np.uint8), pins[3], keep).view(np.uint32)
+    h_mis = _placed(np.full(S * 4, 0xA5, np.uint8), pins[4], keep).view(np.int32)
+    dec = rc.RawErasureDecoder(rc.ECReplicationConfig(k, p))
+    dec.reconstruct_crc_host_batch(h_in, (k + p) * us, us, present, erased, h_out, e * n, n, S, n,
+                                   ck.ChecksumType.CRC32C, bpc, h_ocrc, h_expected=h_exp, h_mismatch=h_mis,
+                                   stripes_per_chunk=_RCHUNK)
+    what = (n, gap, erased, pins, verify)
+    want = np.full(S, -1, np.int32)
+    if verify:
+        want[bad] = read[-1] * nwin + 2
+    assert (h_mis == want).all(), what + (list(h_mis),)
+    assert (h_in.reshape(S, k + p, us) == src).all(), what
+    got, oc = h_out.reshape(S, e, n), h_ocrc.reshape(S, e, nwin)
+    for s in range(S):
+        for i, u in enumerate(erased):
+            if s != bad:  # the bad stripe's rebuilt units are decoded from the corrupted input
+                assert (got[s, i] == units[s, u]).all(), what + (s, u)
+                assert (oc[s, i] == crcs[s, u]).all(), what + (s, u)
+            assert (oc[s, i] == oracle.crc_windows(oracle.CRC32C, got[s, i], bpc)).all(), what + (s, u)
+    for pb in keep:
+        pb.free()
+
+
+@pytest.mark.parametrize("gap", [0, 5])
+@pytest.mark.parametrize("n", [4096, 4099])
+def test_host_batch_ring_reconstruct_forms(n, gap):
+    """ozec_reconstruct_crc_host_batch reading three runs of units (erased [1, 3]) and one run (erased [0]), every
+    buffer pinned, every buffer pageable, and the input pinned differently from the four others: the corrupted window
+    is reported for its stripe only, rebuilt units and their CRC32C equal the originals' and the oracle's."""
+    for erased in ([1, 3], [0]):
+        for pins in ("PPPPP", "UUUUU", "PUUUU", "UPPPP"):
+            _ring_reconstruct(n, gap, erased, pins)
+
+
+def test_host_batch_ring_reconstruct_without_expected():
+    """No stored checksums but a mismatch buffer: every entry reads -1 (nothing was verified)."""
+    _ring_reconstruct(4099, 0, [1, 3], "PUUUU", verify=False)
